@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: 1024² face inversions/sec (100 W+ Adam steps + final OOD/SAIM forward).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]            # N=1 directly; N>1 self-launches N rank processes
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]     # N=1 directly; N>1 self-launches N rank processes
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 One "step" = one pass of the hot path over one batch: B=8 images per GPU (BASELINE.json configs[2]:
@@ -12,8 +12,12 @@ images, encoder latents/features, noise maps) are synthetic (oodgan.synth) and r
 before the timed region.  Multi-GPU = batch sharding (weak scaling): every rank inverts its own 8
 images, the only collective is one all_gather of the finished latents (RCCL over xGMI).
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, measured live with HIP events on
-the launch stream) and `cpu_baseline` (the CPU oracle on the host cores, bounded sample)."""
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports them (`value`,
+`ms_per_step`); everything else is measured only with --full: `roofline` (dominant kernel, measured live with HIP
+events on the launch stream), `cpu_baseline` (the CPU oracle on the host cores, bounded sample), the check of image
+0's loss curve against the reference's, and the secondary legs (single stream, B = 1, LPIPS, precision 'f16s',
+generator forward, encoder, forward only, modconv2d).  --dump-outputs DIR writes what the last timed step returned
+(images, latents, losses) as DIR/<name>.npy."""
 import argparse
 import json
 import os
@@ -31,6 +35,7 @@ if __name__ != '__main__':
 MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: f32-input MFMA = vector peak
 MFMA_F16_PEAK_TFLOPS = 2500.0  # dense f16/bf16 MFMA (spec, MI355X_MICROARCH.md)
 HBM_PEAK_GBPS = 8000.0
+DUMP_MAX_BYTES = 16 << 20      # --dump-outputs: per array; three arrays (images, latents, losses) stay under 64 MB in all
 
 
 def parse():
@@ -60,7 +65,33 @@ def parse():
     ap.add_argument('--no-precision-ab', action='store_true', help="skip the leg that times the same job with precision 'f16s' (3 matrix instructions everywhere)")
     ap.add_argument('--force-launcher', action='store_true',
                     help='start the rank processes from this process even for --gpus 1 (the path `python bench.py --gpus N` takes for N > 1)')
-    return ap.parse_args()
+    ap.add_argument('--full', action='store_true',
+                    help='also run every secondary measurement (rooflines, loss check against the reference curve, the extra legs, CPU baseline); '
+                         'without it the run times the headline workload only and the --no-* leg options have no effect')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one returned (images, latents, losses) to DIR/<name>.npy in float32; '
+                         f'an output larger than {DUMP_MAX_BYTES >> 20} MB as a fixed, seeded sample of its elements (DIR/<name>_sample.npy)')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    return a
+
+
+def dump_outputs(d, arrays):
+    """Write each tensor of ``arrays`` (name -> tensor) to ``d/<name>.npy`` in float32 (float64 stays float64).  A tensor larger
+    than DUMP_MAX_BYTES is written to ``d/<name>_sample.npy`` as its elements at a fixed set of flat indices (a seeded random
+    choice that depends on its element count only, in ascending order), so two builds given the same arguments write
+    comparable files."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        k = DUMP_MAX_BYTES // t.element_size()
+        if t.numel() > k:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+            t, name = t.reshape(-1)[idx.to(t.device)], name + '_sample'
+        np.save(os.path.join(d, name + '.npy'), t.cpu().numpy())
 
 
 def self_launch(a):
@@ -697,12 +728,12 @@ def main():
     torch.cuda.synchronize()
 
     probe = ConvProbe(ops)
-    if not a.no_roofline_events:
+    if a.full and not a.no_roofline_events:
         probe.install()
 
     def one_step():
         out, lats, losses = model.invert(x, steps=a.wsteps, noise=noises, streams=a.streams, use_graph=bool(a.graph), enc_lats=enc_lats, enc_feats=enc_feats)
-        return gather_latents(lats, gB) if dist_on else lats, losses
+        return out, gather_latents(lats, gB) if dist_on else lats, losses
 
     for _ in range(a.warmup):
         one_step()
@@ -714,7 +745,7 @@ def main():
     probe.on = True
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        all_lats, losses = one_step()
+        out, all_lats, losses = one_step()
     torch.cuda.synchronize()
     if dist_on:
         dist.barrier()
@@ -733,6 +764,11 @@ def main():
             per_rank = dict(seconds=[round(float(t[0].item()), 4) for t in allr], cpus_bound=[int(t[1].item()) for t in allr],
                             setup_seconds=[round(float(t[2].item()), 2) for t in allr], torch_threads=[int(t[3].item()) for t in allr])
         dt = tmax.item()
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step: the blended images, the (gathered) refined latents, the loss table
+        dump_outputs(a.dump_outputs, dict(images=out, latents=all_lats, losses=losses))
+    del out         # 100 MB at the default size: not held through the --full legs
+
     def roofline_of(ps, where):
         if not ps:
             return None
@@ -761,7 +797,7 @@ def main():
         roof = roof_timed
         inloop = probe.summary_inloop()
         probe.recs_x = []
-        if a.streams > 1 and not a.no_roofline_events:
+        if a.full and a.streams > 1 and not a.no_roofline_events:
             # A launch duration is a property of the kernel only while the kernel owns the GPU.  The timed region advances
             # sub-batches on concurrent streams (matrix kernels of one beside the HBM-bound producers of the other), so its
             # per-launch durations are inflated by sharing; the roofline of the dominant kernel is therefore taken from an
@@ -785,7 +821,7 @@ def main():
         # ---- the STEP against both roofs (north_star: "throughput ... as fraction of the HBM roofline"): wall time of one W+ step of the
         # timed region = (inversion - final OOD forward) / steps, the OOD forward timed alone right here (HIP events, same inputs)
         step_roof = None
-        if not a.no_roofline_events:
+        if a.full and not a.no_roofline_events:
             model._ood_forward(x, all_lats[:B] if all_lats.shape[0] >= B else enc_lats, enc_feats, noise=noises)
             torch.cuda.synchronize()
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -819,10 +855,10 @@ def main():
                      'forward) / W+ steps; algorithmic bytes / flops: bench.wplus_step_algorithmic (every tensor a launch of the step must read or write, '
                      'once per launch; 2*B*K*M*9*H*W per conv and direction); PMC bytes: 2*FETCH_SIZE + WRITE_SIZE of the step' % B)
         modconv = None
-        if not a.no_modconv and world == 1:
+        if a.full and not a.no_modconv and world == 1:
             modconv = modconv_roofline()
         single = None
-        if not a.no_single_stream and world == 1 and a.streams > 1:
+        if a.full and not a.no_single_stream and world == 1 and a.streams > 1:
             # the same job on ONE stream (every kernel owns the GPU), reported beside `value`
             ss_run = lambda: model.invert(x, steps=a.wsteps, noise=noises, streams=1, enc_lats=enc_lats, enc_feats=enc_feats)
             ss_run()
@@ -851,7 +887,7 @@ def main():
         # gold_wplus_long('wplus_long_1024_bench0'): reference Generator autograd + torch.optim.Adam, fp32)
         loss_check = None
         fx = os.path.join(ROOT, 'tests', 'golden', 'wplus_long_1024_bench0.npz')
-        if rank == 0 and size == 1024 and a.wsteps == 100 and gidx[0] == 0 and os.path.exists(fx):
+        if a.full and size == 1024 and a.wsteps == 100 and gidx[0] == 0 and os.path.exists(fx):
             import numpy as np
             ref = np.load(fx)['losses'][:, 0]
             if ref.shape[0] == 100:
@@ -862,13 +898,13 @@ def main():
                                   reference='reference Generator autograd + torch.optim.Adam, 100 steps, fp32 (tests/golden/wplus_long_1024_bench0.npz)')
                 assert rel[:20].max() < 1e-3 and rel[-1] < 1e-3, f'W+ loss curve of image 0 left the reference band: {loss_check}'
         b1 = None
-        if not a.no_b1 and world == 1:
+        if a.full and not a.no_b1 and world == 1:
             # the reference CLI's mode: one image at a time (run_ood_faceGAN_inversion.py:158-182)
             dt1, ml1 = timed_invert(model, x[:1], [n[:1] for n in noises], enc_lats[:1], [f[:1] for f in enc_feats], streams=1)
             b1 = dict(batch=1, value=round(1.0 / dt1, 4), unit='images/s', ms_per_inversion=round(dt1 * 1e3, 2), ms_per_wplus_step=round(dt1 * 1e3 / max(a.wsteps, 1), 3),
                       final_loss=float(ml1[-1].mean().item()), note=f'B = 1: {a.wsteps} W+ steps + OOD forward of ONE image on one stream')
         lp_leg = None
-        if not a.no_lpips and world == 1:
+        if a.full and not a.no_lpips and world == 1:
             dtl, mll = timed_invert(model, x, noises, enc_lats, enc_feats, streams=a.streams, lpips_weight=0.8)
             terms = model.last_loss_terms
             lp_leg = dict(value=round(B / dtl, 4), unit='images/s', ms_per_step=round(dtl * 1e3, 2), lpips_weight=0.8,
@@ -877,7 +913,7 @@ def main():
                           note='the same inversion with loss = MSE + 0.8 * LPIPS(alex) (north_star: "W+ Adam steps against LPIPS/L2"; oodgan/lpips.py, csrc/lpips.hip: exact-fp32 MFMA '
                                'convs). SEEDED AlexNet / lin weights — the lpips package and its weights are absent (SURVEY §8c): PARITY UNPINNED, timing only; never `value`')
         prec_ab = None
-        if not a.no_precision_ab and world == 1 and a.precision == 'f16s-g2':
+        if a.full and not a.no_precision_ab and world == 1 and a.precision == 'f16s-g2':
             ops.PRECISION = 'f16s'
             try:
                 m3 = ood_faceGAN_e4e(out_size=size, style_dim=512, encoder='E4E', enable_modulation=True, warp_scale=0.08, cycle_align=2, blend_with_gen=True,
@@ -891,17 +927,17 @@ def main():
             finally:
                 ops.PRECISION = a.precision
         gen_b4 = None
-        if not a.no_generator_fwd and world == 1 and size == 1024:
+        if a.full and not a.no_generator_fwd and world == 1 and size == 1024:
             gen_b4 = generator_fwd_b4(a, dev)
         e2e = fwd_only = None
-        if not (a.no_end_to_end and a.no_forward_only) and world == 1 and size == 1024:
+        if a.full and not (a.no_end_to_end and a.no_forward_only) and world == 1 and size == 1024:
             full = build_full_model(a, dev)
             if not a.no_end_to_end:
                 e2e = end_to_end(a, full, x, noises)
             if not a.no_forward_only:
                 fwd_only = forward_only(a, full, x, noises)
             del full
-        cpu = None if (a.no_cpu_baseline or world > 1) else cpu_baseline(size)     # rank 0 at N=1 only
+        cpu = None if (not a.full or a.no_cpu_baseline or world > 1) else cpu_baseline(size)     # rank 0 at N=1 only
         if fwd_only is not None and cpu is not None:
             fwd_only['cpu_baseline'] = dict(ood_forward_s=cpu['ood_forward_s'], cores=cpu['cores'], kind='port', batch=1,
                                             note='CPU oracle, OOD forward after the encoder (the encoder is not part of the oracle)')

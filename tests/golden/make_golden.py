@@ -191,17 +191,22 @@ def gold_generator_narrow(size=64, narrow=0.5):
          narrow=np.float64(narrow), channels=np.asarray([G.channels[str(2 ** i)] for i in range(2, int(np.log2(size)) + 1)]))
 
 
-def gold_wplus(size=32, steps=5):
-    """W+ Adam trajectory through the REFERENCE Generator autograd (SURVEY §8 A9 anchors)."""
+def gold_wplus(size=32, steps=5, dt=torch.float32):
+    """W+ Adam trajectory through the REFERENCE Generator autograd (SURVEY §8 A9 anchors).  ``dt`` float64 (`G.to(dt)`: same
+    reference code) writes ``wplus_s{size}_f64.npz``: in fp32 the W+ gradient at 32² carries rounding that depends on the
+    CPU kernels torch picks (measured against float64: 3.5e-3 of its max with oneDNN's AVX-512 kernels, 1.6e-4 with its
+    AVX2 kernels of the same build), enough to flip Adam's first-step sign of a near-zero coordinate, so only the float64
+    trajectory is the same on every host."""
     from src.ops.StyleGAN.model import Generator
     G = Generator(size, 512, 8).eval()
     G.load_state_dict(synth.generator_state(size, seed=5), strict=True)
+    G = G.to(dt)
     for p in G.parameters():
         p.requires_grad_(False)
     B = 2
-    target = synth.make_images(size, B, seed=9)
-    noises = synth.make_noises(size, B, seed=7)
-    w = synth.make_latents(size, B, seed=6).clone().requires_grad_(True)
+    target = synth.make_images(size, B, seed=9).to(dt)
+    noises = [n.to(dt) for n in synth.make_noises(size, B, seed=7)]
+    w = synth.make_latents(size, B, seed=6).to(dt).clone().requires_grad_(True)
     opt = torch.optim.Adam([w], lr=0.01, betas=(0.9, 0.999), eps=1e-8)
     losses, traj, grads = [], [], []
     for _ in range(steps):
@@ -213,7 +218,7 @@ def gold_wplus(size=32, steps=5):
         grads.append(w.grad.detach().clone())
         opt.step()
         traj.append(w.detach().clone())
-    save(f'wplus_s{size}.npz', losses=torch.stack(losses), traj=torch.stack(traj), grads=torch.stack(grads))
+    save(f'wplus_s{size}{"_f64" if dt == torch.float64 else ""}.npz', losses=torch.stack(losses), traj=torch.stack(traj), grads=torch.stack(grads))
 
 
 WPLUS_1024_IMAGE = 10     # global image index of the bench recipe (bench.py: weights seed 0, target 1000+g, noise 2000+g, latents 3000+g)
@@ -735,6 +740,7 @@ def main():
         gold_generator_narrow(1024, 0.25)
     if 'wplus' in which:
         gold_wplus(32, 5)
+        gold_wplus(32, 5, torch.float64)
     if 'wplus1024' in which:
         gold_wplus_1024()
     if 'genb4' in which:

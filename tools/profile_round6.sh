@@ -8,7 +8,7 @@ TAG=${1:-prof}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-LEGS="--no-cpu-baseline --no-modconv --no-single-stream --no-end-to-end --no-forward-only --no-generator-fwd --no-b1 --no-lpips --no-precision-ab"
+LEGS="--full --no-cpu-baseline --no-modconv --no-single-stream --no-end-to-end --no-forward-only --no-generator-fwd --no-b1 --no-lpips --no-precision-ab"
 SHORT="--wsteps 10 --steps 1 --warmup 1 $LEGS --streams 1 --no-plan"
 rocprofv3 --kernel-trace -d $OUT/stats_s1 -o k -- python3 bench.py --streams 1 $LEGS > $OUT/bench_s1.json 2> $OUT/bench_s1.err
 rocprofv3 --kernel-trace -d $OUT/stats_s2 -o k -- python3 bench.py $LEGS > $OUT/bench_sN.json 2> $OUT/bench_sN.err
