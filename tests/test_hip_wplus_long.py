@@ -96,6 +96,19 @@ def test_100_steps_256_vs_reference_adam(dev, prec):
     assert torch.isfinite(w).all()
 
 
+# 1024², 100 steps: bars at <= 4x the values this build prints (the kernels are run-to-run bit-reproducible, so they are stable on one
+# build) — rms distance of w_100 to the reference's over the rms distance the reference moved from w0, and the rms of G(w_100) - the
+# reference's G(w_100) over the image std.  Measured (w ratio, image ratio):
+W100_BAR = {('wplus_long_1024.npz', 'f16s'): 4e-3,            # 1.04e-3
+            ('wplus_long_1024.npz', 'f16s-g2'): 1e-2,         # 2.57e-3
+            ('wplus_long_1024_img0.npz', 'f16s'): 4e-3,       # 1.10e-3
+            ('wplus_long_1024_img0.npz', 'f16s-g2'): 3.5e-3}  # 9.94e-4
+IMG100_BAR = {('wplus_long_1024.npz', 'f16s'): 4e-3,          # 1.01e-3
+              ('wplus_long_1024.npz', 'f16s-g2'): 9e-3,       # 2.29e-3
+              ('wplus_long_1024_img0.npz', 'f16s'): 4e-3,     # 1.04e-3
+              ('wplus_long_1024_img0.npz', 'f16s-g2'): 3.5e-3}  # 9.04e-4
+
+
 @pytest.mark.parametrize('prec', ['f16s', 'f16s-g2'])
 @pytest.mark.parametrize('fixture', ['wplus_long_1024.npz', 'wplus_long_1024_img0.npz'])
 def test_100_steps_1024_vs_reference_adam(dev, prec, fixture):
@@ -133,16 +146,18 @@ def test_100_steps_1024_vs_reference_adam(dev, prec, fixture):
     for t in (10, 30, 100):
         dw = (w.double().cpu() - g32[f'w_step{t}']).abs() if t == 100 else None
         if dw is not None:
+            moved = float((g32['w_step100'] - w0.double().cpu()).pow(2).mean().sqrt())
             print(f'[1024² {prec}] w at step 100: rms distance {float(dw.pow(2).mean().sqrt()):.2e}, within 2e-3: {float((dw < 2e-3).double().mean()):.4f}, '
-                  f'moved from w0 by rms {float((g32["w_step100"] - w0.double().cpu()).pow(2).mean().sqrt()):.2e}')
-            assert float(dw.pow(2).mean().sqrt()) < 0.25 * float((g32['w_step100'] - w0.double().cpu()).pow(2).mean().sqrt())
+                  f'moved from w0 by rms {moved:.2e} (ratio {float(dw.pow(2).mean().sqrt()) / moved:.2e})')
+            assert float(dw.pow(2).mean().sqrt()) < W100_BAR[fixture, prec] * moved
     # G(w_100) of THIS build against the reference's G(w_100): the images the two inversions end on
     img = eng.forward(w, noises)
     sub = img[:, :, ::16, ::16].double().cpu()
     e_img = float((sub - g32['final_image_sub'].double()).abs().max())
     e_rms = float((sub - g32['final_image_sub'].double()).pow(2).mean().sqrt())
-    print(f'[1024² {prec}] G(w_100) vs the reference\'s: max |d pixel| {e_img:.2e}, rms {e_rms:.2e} (image std {float(g32["final_image_std"].mean()):.2f})')
-    assert e_rms < 0.02 * float(g32['final_image_std'].mean())
+    print(f'[1024² {prec}] G(w_100) vs the reference\'s: max |d pixel| {e_img:.2e}, rms {e_rms:.2e} (image std {float(g32["final_image_std"].mean()):.2f}, '
+          f'rms / std {e_rms / float(g32["final_image_std"].mean()):.2e})')
+    assert e_rms < IMG100_BAR[fixture, prec] * float(g32['final_image_std'].mean())
 
 
 def test_two_streams_and_one_stream_end_on_the_same_loss_b8(dev):
