@@ -60,7 +60,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), and "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);
@@ -589,6 +589,27 @@ int oodgan_mse_nparts(long CHW);
  * recorded step (oodgan_plan_run, hipGraph replay) fills the loss table row by row without a host-side pointer per step */
 int oodgan_mse_fwd_bwd_row(const float* img, const float* target, float* gimg, float* part, float* loss_table,
                            const int* row_dev, int nrows, int B, long CHW, float grad_mul, void* stream);
+/* Masked objective: the loss is taken on the composite c = x + beta*(G - x), beta (B,1,HW) in [0,1] one plane per image,
+ * broadcast over the C channels.  replaces: the reference's blending_mask + blend applied blend_cnt times
+ * (src/archs/OOD_faceGAN_e4e_arch.py:305-307,315-347: out - x = (1-alpha)^n (G - x)) as the target of basicsr's MSELoss
+ * (BasicSR/basicsr/losses/losses.py:58-83) — the reference's own loop fits the raw G; the composite is this build's objective.
+ * d = beta*(img - target); loss[b] = mean_{c,p} d^2 (two-stage partial sums, no float atomics: part (B, oodgan_mse_nparts(C*HW)));
+ * gimg = grad_mul*2/(C*HW) * d (the gradient w.r.t. c) or, with wrt_gen = 1, that times beta (w.r.t. img); gimg may be NULL;
+ * comp (B,C,HW) or NULL receives c.  beta == 1, C == 3: loss and gimg are bit-identical to oodgan_mse_fwd_bwd.  Counted by the
+ * dispatch counter "composite_mse". */
+int oodgan_composite_mse_fwd_bwd(const float* img, const float* target, const float* beta, float* gimg, float* comp, float* part,
+                                 float* loss, int B, int C, long HW, int wrt_gen, float grad_mul, void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_composite_mse_fwd_bwd_row(const float* img, const float* target, const float* beta, float* gimg, float* comp, float* part,
+                                     float* loss_table, const int* row_dev, int nrows, int B, int C, long HW, int wrt_gen,
+                                     float grad_mul, void* stream);
+/* g (B,C,HW) <- beta (B,1,HW) (.) g in place: the chain rule from the composite to the generator output once the LPIPS term
+ * (oodgan_lpips_img_grad, which accumulates) has added its part of dL/dc.  replaces: autograd through `alpha*x + out*(1-alpha)`
+ * (OOD_faceGAN_e4e_arch.py:346) */
+int oodgan_scale_by_plane(float* g, const float* beta, int B, int C, long HW, void* stream);
+/* beta[i] = clip(1 - alpha[i], 0, 1)^power (n elements): the loss weight of the composite `blend` applied `power` times makes from
+ * the mask of blending_mask (OOD_faceGAN_e4e_arch.py:315-339, its clip kept) */
+int oodgan_loss_weight_from_alpha(const float* alpha, float* beta, long n, int power, void* stream);
 /* torch.optim.Adam step (no weight decay, no amsgrad), step index t>=1 given by the host:
  * anchors: get_optimizer (src/models/OOD_faceGAN_model.py:398-400). */
 int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,

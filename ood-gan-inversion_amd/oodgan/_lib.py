@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 109
+ABI_VERSION = 110
 
 
 class ConvArgs(Structure):
@@ -165,6 +165,10 @@ _SIGS = {
     'oodgan_plan_run': (c_int, [P, c_int]),
     'oodgan_plan_set_null_launch': (c_int, [c_int]),
     'oodgan_mse_nparts': (c_int, [c_long]),
+    'oodgan_composite_mse_fwd_bwd': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
+    'oodgan_composite_mse_fwd_bwd_row': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_long, c_int, c_float, P]),
+    'oodgan_scale_by_plane': (c_int, [P, P, c_int, c_int, c_long, P]),
+    'oodgan_loss_weight_from_alpha': (c_int, [P, P, c_long, c_int, P]),
     'oodgan_adam_step': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_int, P]),
     'oodgan_adam_step_dev': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, P]),
 }
@@ -217,7 +221,8 @@ def set_tunable(name, value):
 
 
 def dispatch_count(name):
-    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` since load / dispatch_reset() (include/oodgan.h)."""
+    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse") since load /
+    dispatch_reset() (include/oodgan.h)."""
     n = lib().oodgan_dispatch_count(name.encode())
     if n < 0:
         raise RuntimeError(f'unknown dispatch counter {name!r}')

@@ -218,6 +218,16 @@ class ood_faceGAN_e4e(nn.Module):
         if self.modulation is None:
             out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise)
             return out, lats
+        out = self._hooked_generate(lats, enc_feats, noise)
+        if self.blend_with_gen:
+            if self.skip_SA:
+                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise)
+            for _ in range(self.blend_cnt):
+                out = self.blend(x, out, alpha_scale=None)
+        return out, lats
+
+    def _hooked_generate(self, lats, enc_feats, noise):
+        """The generator pass with the SAMM hooks (e4e :268-297): fills ``self.aligns`` with the per-level fields; returns G's image."""
         self.feats = [samm.conv1x1(enc_feats[i], self.feats_conv[i].weight, self.feats_conv[i].bias) for i in range(4)]
         self.lats = lats
         self.aligns = {}
@@ -226,12 +236,7 @@ class ood_faceGAN_e4e(nn.Module):
         out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, conditions=conditions,
                                 cond_layers=cond_ind, cond_type=self.modulation_type, cond_hook=self._cond_hook,
                                 noise=noise)
-        if self.blend_with_gen:
-            if self.skip_SA:
-                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise)
-            for _ in range(self.blend_cnt):
-                out = self.blend(x, out, alpha_scale=None)
-        return out, lats
+        return out
 
     def blending_mask(self):
         """:315-339 — compose the up-sampled alpha channels (coarse -> fine), clip; stores aligns[size]."""
@@ -256,7 +261,8 @@ class ood_faceGAN_e4e(nn.Module):
         return out
 
     # ---------------------------------------------------------------- build-defined: W+ refinement
-    def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, **kwargs):
+    def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
+               **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -270,11 +276,18 @@ class ood_faceGAN_e4e(nn.Module):
         stream count or an image's position in the batch — kernel selection follows the sub-batch geometry (8-wave
         kernels from 128 work items) and every sub-batch carries its own range scales — the difference is fp32
         rounding on the first step (loss within 1e-5 relative) and Adam's sign choice for ~0 gradient coordinates afterwards
-        (0.003 % of the coordinates, losses within 1e-3 relative after three steps: ``tests/test_hip_generator.py``)."""
+        (0.003 % of the coordinates, losses within 1e-3 relative after three steps: ``tests/test_hip_generator.py``).
+        ``loss_region``: where the W+ loss looks.  'full' (default): every pixel, the plain per-image MSE.  'blend': the
+        composite x + beta*(G(w) - x) with beta = (1 - alpha0)^blend_cnt, alpha0 the mask of the OOD forward at the start latents with the
+        same ``noise`` — the error of the blended output this method returns, with the mask frozen for the run.  A float32 (B,1,S,S) tensor
+        in [0,1] on the model's device: that beta (a caller mask: 0 = ignore the pixel).  ``self.last_loss_weight`` is the beta optimised
+        (None for 'full')."""
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
         if noise is None:
             noise = [n.expand(B, -1, -1, -1).contiguous() for n in self.generator.make_noise()]
+        beta = self._loss_weight(loss_region, x, lats0, enc_feats, noise)
+        self.last_loss_weight = beta
         lp = None
         if lpips_weight:
             # loss = MSE + lpips_weight * LPIPS(alex) (reference loss class: src/losses/lpips_loss.py:13-34, min_max = the generator's (-1, 1)).
@@ -287,7 +300,7 @@ class ood_faceGAN_e4e(nn.Module):
                 self._lpips_net, self._lpips_key = LPIPSAlex({k: v.to(x.device) for k, v in st.items()}, min_max=(-1.0, 1.0)), key
             lp = self._lpips_net
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight)
-        w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph)
+        w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise')}
         out, lats = self._ood_forward(x, w, enc_feats, noise=noise, **kw)
@@ -298,6 +311,31 @@ class ood_faceGAN_e4e(nn.Module):
         # carried-scale flag in Generator.forward happened to provide this synchronisation)
         torch.cuda.current_stream().synchronize()
         return out, lats, losses
+
+    def _loss_weight(self, loss_region, x, lats0, enc_feats, noise):
+        """beta of ``invert(loss_region=...)``: None for 'full'; for 'blend' the mask of one hooked generator pass at the start latents
+        (blending_mask, then oodgan_loss_weight_from_alpha); a tensor is checked and returned."""
+        S = self.generator.size
+        if isinstance(loss_region, torch.Tensor):
+            beta = loss_region
+            if tuple(beta.shape) != (x.shape[0], 1, S, S) or beta.dtype != torch.float32 or beta.device != x.device:
+                raise ValueError(f'loss_region tensor must be float32 of shape {(x.shape[0], 1, S, S)} on {x.device}, got '
+                                 f'{beta.dtype} {tuple(beta.shape)} on {beta.device}')
+            lo, hi = torch.aminmax(beta)
+            if not (lo.item() >= 0.0 and hi.item() <= 1.0):         # NaN fails both
+                raise ValueError(f'loss_region tensor values must lie in [0, 1], got [{lo.item()}, {hi.item()}]')
+            return beta.contiguous()
+        if loss_region == 'full':
+            return None
+        if loss_region != 'blend':
+            raise ValueError(f"loss_region must be 'full', 'blend' or a (B,1,S,S) tensor, got {loss_region!r}")
+        if self.modulation is None or not self.blend_with_gen:
+            raise ValueError("loss_region='blend' needs enable_modulation=True and blend_with_gen=True: without them there is no blend")
+        # alpha0 is frozen for the run: refreshing it would need the OOD forward (which shares the engine's carried range state) between
+        # recorded steps (DESIGN.md §5).  The W+ loop resets that state before its first step, so this pass leaves nothing behind for it
+        self._hooked_generate(lats0, enc_feats, noise)
+        alpha = self.blending_mask()
+        return ops.loss_weight_from_alpha(alpha, self.blend_cnt)
 
 
 class GraphedForward:

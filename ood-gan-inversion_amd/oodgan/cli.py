@@ -12,6 +12,13 @@ and, when the build-defined block ``inversion: {wplus_steps: N, lr: 0.01, batch:
 present, refines the encoder latents with N W+ Adam steps before the OOD forward (``streams: S``
 in the same block advances the loop on S concurrent HIP streams, default 1; ``graph: true`` replays the plain forward from a
 captured hipGraph).
+Where the W+ loss looks, in the same block:
+
+    loss_region: full | blend    full (default): every pixel.  blend: the blended output the model returns, x + beta*(G - x) with
+                                 beta = (1 - alpha)^blend_cnt from the mask of the OOD forward at the start latents.
+    mask_dir: <dir>              a caller mask per input file: <dir>/<base name>.png (grayscale; the first channel / 255 is beta,
+                                 0 = ignore the pixel), resized nearest to the generator size.  A file without a mask is an error.
+                                 Excludes ``loss_region: blend``.
 ``model_dict`` holds the reference's three variants (run_ood_faceGAN_inversion.py:23-27): the ``network_g`` blocks of
 options/test/{E4E,ReStyle,FeatureStyle}_Face_test.yml resolve unchanged.  LPIPS / identity need third-party weights that
 do not ship: they are reported as skipped."""
@@ -57,6 +64,35 @@ def load_files_from_path(opt, directions_dir=None):
     return [os.path.join(root, n) for n in names], load_direction(directions_dir, opt.get('editing'))
 
 
+def mask_to_weight(mask, size):
+    """An HxW(xC) mask image (uint8 values 0..255; the first channel is read) -> the (1,1,size,size) float32 loss weight mask/255, resized
+    nearest (F.interpolate(mode='nearest'): src = floor(dst*in/out))."""
+    m = np.asarray(mask)
+    if m.ndim == 3:
+        m = m[:, :, 0]
+    if m.ndim != 2 or m.size == 0:
+        raise ValueError(f'a loss mask must be an HxW or HxWxC image, got shape {np.asarray(mask).shape}')
+    m = m.astype(np.float64)
+    if not (np.isfinite(m).all() and m.min() >= 0.0 and m.max() <= 255.0):
+        raise ValueError(f'loss mask values must lie in [0, 255], got [{m.min()}, {m.max()}]')
+    H, W = m.shape
+    rows = (np.arange(size) * H) // size
+    cols = (np.arange(size) * W) // size
+    beta = (m[rows][:, cols] / 255.0).astype(np.float32)
+    return torch.from_numpy(np.ascontiguousarray(beta)).reshape(1, 1, size, size)
+
+
+def load_loss_weights(files, mask_dir, size):
+    """beta (B,1,size,size) float32 for the input ``files``: <mask_dir>/<base name>.png each (``mask_to_weight``); a missing mask raises."""
+    out = []
+    for f in files:
+        path = os.path.join(mask_dir, os.path.splitext(os.path.basename(f))[0] + '.png')
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f'inversion.mask_dir: no mask {path} for input {f}')
+        out.append(mask_to_weight(imgio.imread(path)[:, :, ::-1], size))     # imread gives BGR: its last channel is the file's first
+    return torch.cat(out, 0)
+
+
 def evaluate(gt_bgr, res_bgr, metrics, opt):
     """:89-126 — gt and result as [0,255] BGR arrays."""
     if metrics is None:
@@ -73,12 +109,17 @@ def evaluate(gt_bgr, res_bgr, metrics, opt):
 
 def run(opts, wplus_steps=None, log=None):
     log = log or logging.getLogger('oodgan.cli')
+    inv = opts.get('inversion') or {}
+    loss_region, mask_dir = inv.get('loss_region', 'full'), inv.get('mask_dir')
+    if loss_region not in ('full', 'blend'):
+        raise ValueError(f"inversion.loss_region must be 'full' or 'blend', got {loss_region!r}")
+    if mask_dir and loss_region != 'full':
+        raise ValueError('inversion.mask_dir and inversion.loss_region: blend exclude each other')
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
     model = load_model(opts).cuda().eval()
     directions_dir = opts.get('directions_dir', './directions')
     save_root = os.path.join(opts.get('save_dir', './results'), opts['name'])
-    inv = opts.get('inversion') or {}
     steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     lr = float(inv.get('lr', 0.01))
     streams = int(inv.get('streams', 1))
@@ -105,10 +146,12 @@ def run(opts, wplus_steps=None, log=None):
             chunk = files[c0:c0 + nb]
             bgrs = [imgio.imread(f).astype(np.float64) for f in chunk]
             x = torch.cat([imgio.image_to_input(bgr, size, device='cuda') for bgr in bgrs], 0)
+            region = load_loss_weights(chunk, mask_dir, size).cuda() if (mask_dir and steps > 0) else loss_region
             with torch.no_grad():
                 t0 = time.time()
                 if steps > 0:
-                    out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state)[0]
+                    out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
+                                       loss_region=region)[0]
                 else:
                     out = (graphed(x) if graphed is not None else model(x))[0]
                 torch.cuda.synchronize()

@@ -765,9 +765,12 @@ class _WRun:
     snapshot becomes the last clean state.  Set: the run goes back to the last clean state, repeats that window (<= check_every steps)
     with exact scales, and continues in carry mode from freshly measured scales."""
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, dev_counter, keep_traj):
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, dev_counter, keep_traj, beta=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
+        # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
+        # replays it unchanged; a rollback needs nothing new: it is constant for the run); None = the plain per-image MSE
+        self.beta = beta
         self.w = w0.detach().clone().contiguous()
         self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
         self.gmul = ops.loss_scale_for(target.numel() // target.shape[0])
@@ -801,7 +804,14 @@ class _WRun:
     def _eager_step(self):
         eng, inv = self.eng, self.inv
         img = eng.forward(self.w, self.noises, save=True, range_mode='carry')
-        if self.dev_t is not None:
+        if self.beta is not None:
+            gimg = self._masked_loss(img)
+            g = eng.backward(gimg, self.gmul, carry_scale=True)
+            if self.dev_t is not None:
+                ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
+            else:
+                ops.adam_step(self.w, g, self.m, self.v, self.t + 1, inv.lr, inv.betas, inv.eps)
+        elif self.dev_t is not None:
             # loss row and Adam's step index from the device counter: the recorded step is the same launch list for every t
             _, gimg = ops.mse_loss_grad(img, self.target, self.gmul, table=self.lbuf, row_dev=self.dev_t)
             if self.lp is not None:     # gimg += gmul * lambda * d(sum_b lpips_b)/d(img); values to row t of the second table
@@ -814,6 +824,25 @@ class _WRun:
                 self.lp_table[self.t].copy_(self.lp.loss_and_grad(img, gimg, inv.lpips_weight * self.gmul, target_taps=self.lp_target))
             g = eng.backward(gimg, self.gmul, carry_scale=True)
             ops.adam_step(self.w, g, self.m, self.v, self.t + 1, inv.lr, inv.betas, inv.eps)
+
+    def _masked_loss(self, img):
+        """The composite loss of the step and its gradient w.r.t. the generator output.  Without LPIPS one kernel writes beta*dL/dc; with it the
+        kernel writes dL/dc and the composite c, LPIPS(c, x) adds its part of dL/dc, and beta is applied once afterwards."""
+        inv, lp = self.inv, self.lp
+        wrt = 'gen' if lp is None else 'composite'
+        if self.dev_t is not None:
+            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=lp is not None,
+                                                        table=self.lbuf, row_dev=self.dev_t)
+            if lp is not None:
+                lp.loss_and_grad(comp, gimg, inv.lpips_weight * self.gmul, table=self.lp_table, row_dev=self.dev_t, target_taps=self.lp_target)
+        else:
+            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=lp is not None,
+                                                        loss_out=self.lbuf[self.t])
+            if lp is not None:
+                self.lp_table[self.t].copy_(lp.loss_and_grad(comp, gimg, inv.lpips_weight * self.gmul, target_taps=self.lp_target))
+        if lp is not None:
+            ops.scale_by_plane(gimg, self.beta)
+        return gimg
 
     def _step(self):
         eng = self.eng
@@ -952,11 +981,20 @@ class WPlusInverter:
             self._pins.append(torch.zeros(2, dtype=torch.int32).pin_memory())
         return self._pins[i]
 
-    def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False):
+    def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
-        then share the GPU with the matrix kernels of the other instead of running back to back."""
+        then share the GPU with the matrix kernels of the other instead of running back to back.
+        ``loss_weight``: None (the per-image MSE) or a float32 (B,1,S,S) plane beta in [0,1] on the device — the loss is then taken on the
+        composite c = target + beta*(G(w) - target); a pixel with beta = 0 has no influence on the run."""
         B = w0.shape[0]
+        if loss_weight is not None:
+            if tuple(loss_weight.shape) != (B, 1) + tuple(target.shape[2:]) or loss_weight.dtype != torch.float32 or loss_weight.device != target.device:
+                raise ValueError(f'loss_weight must be a float32 {(B, 1) + tuple(target.shape[2:])} tensor on {target.device}, got '
+                                 f'{loss_weight.dtype} {tuple(loss_weight.shape)} on {loss_weight.device}')
+            loss_weight = loss_weight.contiguous()
+            if use_graph:
+                raise NotImplementedError('use_graph with a loss weight: use the launch plans (default) instead')
         streams = max(1, min(int(streams), B))
         if B == 0:          # an empty shard (oodgan/parallel.py hands a rank with no images an empty batch): nothing to launch
             steps = 0
@@ -969,7 +1007,7 @@ class WPlusInverter:
         if use_graph:
             return self._invert_graph(target, w0, noises, steps, streams)
         if streams == 1:
-            return self._invert_runs(target, w0, noises, steps, 1, return_trajectory)
+            return self._invert_runs(target, w0, noises, steps, 1, return_trajectory, loss_weight)
         from . import _lib
         # the multi-stream threshold of the 8-wave stride-1 kernel, unless the caller set the tunable itself; the value that was read is
         # the one restored
@@ -978,19 +1016,19 @@ class WPlusInverter:
         if override:
             _lib.set_tunable('s1_big_min_items', MULTI_STREAM_S1_BIG_MIN_ITEMS)
         try:
-            return self._invert_runs(target, w0, noises, steps, streams, False)
+            return self._invert_runs(target, w0, noises, steps, streams, False, loss_weight)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', old)
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory):
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, beta=None):
         B = w0.shape[0]
         self._runs = []
         if streams == 1:
             eng = self.engine
             eng.reset_bwd_state()
             eng.reset_fwd_state()
-            runs = [_WRun(self, eng, target, w0, noises, steps, None, self.use_plan and not return_trajectory, return_trajectory)]
+            runs = [_WRun(self, eng, target, w0, noises, steps, None, self.use_plan and not return_trajectory, return_trajectory, beta)]
         else:
             cur = torch.cuda.current_stream()
             side = _side_streams(w0.device, streams)
@@ -1006,13 +1044,13 @@ class WPlusInverter:
             for i in range(streams):
                 sl = slice(cuts[i], cuts[i + 1])
                 parts.append((target[sl].contiguous(), w0[sl].detach().contiguous(),
-                              [n[sl].contiguous() if n.shape[0] == B else n for n in noises]))
+                              [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous()))
             for st in side:
                 st.wait_stream(cur)                 # AFTER the slices above were enqueued on the caller's stream
             runs = []
             for i, st in enumerate(side):
                 with torch.cuda.stream(st):         # state tensors initialised on the stream that uses them
-                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, True, False))
+                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, True, False, parts[i][3]))
         try:
             busy = True
             while busy:

@@ -1230,6 +1230,60 @@ def mse_loss_grad(img, target, grad_mul=1.0, loss_out=None, table=None, row_dev=
     return loss, g
 
 
+def _plane(beta, img, name='beta'):
+    """beta (B,1,H,W) float32 on the image's device, one plane per image of ``img`` (B,C,H,W)."""
+    w = _dev(beta, name)
+    B, C, H, W = img.shape
+    if tuple(w.shape) != (B, 1, H, W):
+        raise ValueError(f'{name} must have shape {(B, 1, H, W)} for images {tuple(img.shape)}, got {tuple(w.shape)}')
+    return w
+
+
+def composite_mse_loss_grad(img, target, beta, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None, row_dev=None):
+    """The masked objective (oodgan_composite_mse_fwd_bwd): with c = target + beta*(img - target), per-image loss mean((c - target)^2) and its
+    gradient times grad_mul, w.r.t. the generator output (``wrt='gen'``) or w.r.t. the composite (``wrt='composite'``: the LPIPS term adds to it,
+    then ``scale_by_plane`` applies beta).  ``composite=True`` also returns c.  Returns (loss[B] or None with ``table``, gimg, c or None);
+    ``loss_out`` / ``table`` + ``row_dev``: as ``mse_loss_grad``.  beta == 1 gives mse_loss_grad's loss and gradient bit for bit."""
+    a, t = _dev(img, 'img'), _dev(target, 'target')
+    w = _plane(beta, a)
+    if wrt not in ('gen', 'composite'):
+        raise ValueError(f"wrt must be 'gen' or 'composite', got {wrt!r}")
+    B, C, H, W = a.shape
+    L = _lib.lib()
+    part = torch.empty(B, L.oodgan_mse_nparts(C * H * W), device=a.device, dtype=torch.float32)
+    g = torch.empty_like(a)
+    c = torch.empty_like(a) if composite else None
+    gen = 1 if wrt == 'gen' else 0
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and row_dev.dtype == torch.int32
+        check(L.oodgan_composite_mse_fwd_bwd_row(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(table), _p(row_dev), table.shape[0], B, C, H * W,
+                                                 gen, float(grad_mul), _stream()), 'composite_mse_row')
+        return None, g, c
+    loss = torch.empty(B, device=a.device, dtype=torch.float32) if loss_out is None else loss_out
+    assert loss.shape == (B,) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == a.device
+    check(L.oodgan_composite_mse_fwd_bwd(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(loss), B, C, H * W, gen, float(grad_mul), _stream()),
+          'composite_mse')
+    return loss, g, c
+
+
+def scale_by_plane(g, beta):
+    """g (B,C,H,W) <- beta (B,1,H,W) * g in place (oodgan_scale_by_plane); returns g."""
+    assert g.is_contiguous(), 'scale_by_plane: g must be contiguous (it is updated in place)'
+    w = _plane(beta, _dev(g, 'g'))
+    B, C, H, W = g.shape
+    check(_lib.lib().oodgan_scale_by_plane(_p(g), _p(w), B, C, H * W, _stream()), 'scale_by_plane')
+    return g
+
+
+def loss_weight_from_alpha(alpha, power=1):
+    """beta = clip(1 - alpha, 0, 1)^power (oodgan_loss_weight_from_alpha): the loss weight of the composite that ``blend`` applied ``power`` times
+    produces from the mask ``alpha`` (B,1,S,S) of ``blending_mask``."""
+    a = _dev(alpha, 'alpha')
+    beta = torch.empty_like(a)
+    check(_lib.lib().oodgan_loss_weight_from_alpha(_p(a), _p(beta), a.numel(), int(power), _stream()), 'loss_weight_from_alpha')
+    return beta
+
+
 class LaunchPlan:
     """oodgan_plan_* (include/oodgan.h): the kernel launches this thread makes inside ``with plan.recording():`` — through any op of this
     module — recorded once and re-issued from C++ by ``run()``; eager launches on the streams they were recorded with.  The caller keeps
