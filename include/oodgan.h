@@ -60,7 +60,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), and "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]) and "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);
@@ -610,6 +610,21 @@ int oodgan_scale_by_plane(float* g, const float* beta, int B, int C, long HW, vo
 /* beta[i] = clip(1 - alpha[i], 0, 1)^power (n elements): the loss weight of the composite `blend` applied `power` times makes from
  * the mask of blending_mask (OOD_faceGAN_e4e_arch.py:315-339, its clip kept) */
 int oodgan_loss_weight_from_alpha(const float* alpha, float* beta, long n, int power, void* stream);
+/* SSIM term of the W+ loss: loss[b] = 1 - SSIM_b for img, target (B,C,H,W) float32 in the generator's [-1,1] range
+ * (unclamped, unrounded), SSIM_b = the mean over the C channels and the valid (H-10)x(W-10) window positions of
+ * ((2 mu_v mu_y + c1)(2 s_vy + c2)) / ((mu_v^2 + mu_y^2 + c1)(s_v^2 + s_y^2 + c2)) on v = 127.5(img+1), y = 127.5(target+1) under the
+ * normalised 11-tap Gaussian window (sigma 1.5), c1 = (0.01*255)^2, c2 = (0.03*255)^2.  anchors: calculate_ssim / _ssim
+ * (BasicSR/basicsr/metrics/psnr_ssim.py:49-128) with crop_border = 0, test_y_channel = False, on float images — the reference only
+ * reports the metric; as a loss term it is this build's.
+ * gimg (B,C,H,W) or NULL: gimg += grad_mul * d(sum_b loss[b])/d(img), ACCUMULATED into what the MSE kernel wrote (the contract of
+ * oodgan_lpips_img_grad); NULL = forward only, the same value bit for bit.  part: (B, oodgan_ssim_nparts(C,H,W)) scratch; two-stage
+ * sums, no float atomics: bit-reproducible.  H or W < 11: OODGAN_E_ARG.  Counted by the dispatch counter "ssim". */
+int oodgan_ssim_loss_fwd_bwd(const float* img, const float* target, float* gimg, float* part, float* loss, int B, int C, int H, int W,
+                             float grad_mul, void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_ssim_loss_fwd_bwd_row(const float* img, const float* target, float* gimg, float* part, float* loss_table, const int* row_dev,
+                                 int nrows, int B, int C, int H, int W, float grad_mul, void* stream);
+int oodgan_ssim_nparts(int C, int H, int W);
 /* torch.optim.Adam step (no weight decay, no amsgrad), step index t>=1 given by the host:
  * anchors: get_optimizer (src/models/OOD_faceGAN_model.py:398-400). */
 int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,

@@ -46,7 +46,9 @@ enum { OODGAN_DC_STRIPX = 0, OODGAN_DC_STRIP, OODGAN_DC_S1BIG, OODGAN_DC_S1V2, O
        // round 6: input-gradient launches with oodgan_conv_args.x_hi_only (two matrix instructions per product)
        OODGAN_DC_S1BIG_G2, OODGAN_DC_S2BIG_G2, OODGAN_DC_STRIPX_G2, OODGAN_DC_S2BIG_XH, OODGAN_DC_S1BIG_XH,
        // calls of the masked-loss kernel (loss_masked.hip, oodgan_composite_mse_fwd_bwd[_row])
-       OODGAN_DC_COMPOSITE_MSE, OODGAN_DC_COUNT };
+       OODGAN_DC_COMPOSITE_MSE,
+       // calls of the SSIM loss kernel (loss_ssim.hip, oodgan_ssim_loss_fwd_bwd[_row])
+       OODGAN_DC_SSIM, OODGAN_DC_COUNT };
 void count_dispatch(int id);
 
 // One process per GPU: per-kernel setup (dynamic-LDS attributes, the zero page and CU count of the F-form strip

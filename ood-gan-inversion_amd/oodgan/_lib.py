@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 110
+ABI_VERSION = 111
 
 
 class ConvArgs(Structure):
@@ -169,6 +169,9 @@ _SIGS = {
     'oodgan_composite_mse_fwd_bwd_row': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_long, c_int, c_float, P]),
     'oodgan_scale_by_plane': (c_int, [P, P, c_int, c_int, c_long, P]),
     'oodgan_loss_weight_from_alpha': (c_int, [P, P, c_long, c_int, P]),
+    'oodgan_ssim_nparts': (c_int, [c_int, c_int, c_int]),
+    'oodgan_ssim_loss_fwd_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
+    'oodgan_ssim_loss_fwd_bwd_row': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     'oodgan_adam_step': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_int, P]),
     'oodgan_adam_step_dev': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, P]),
 }
@@ -221,7 +224,7 @@ def set_tunable(name, value):
 
 
 def dispatch_count(name):
-    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse") since load /
+    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", or the SSIM loss kernel, "ssim") since load /
     dispatch_reset() (include/oodgan.h)."""
     n = lib().oodgan_dispatch_count(name.encode())
     if n < 0:

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter
+from .engine import WPlusInverter, check_ssim_weight
 from .modules import Generator
 from .synth import generator_channels
 
@@ -262,11 +262,14 @@ class ood_faceGAN_e4e(nn.Module):
 
     # ---------------------------------------------------------------- build-defined: W+ refinement
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
-               **kwargs):
+               ssim_weight=0.0, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
-        loss (opt-in; ``losses`` is then the total, ``self.last_loss_terms`` holds the two tables).
+        loss (opt-in; ``losses`` is then the total, ``self.last_loss_terms`` holds the tables).
+        ``ssim_weight`` > 0 adds that multiple of 1 - SSIM per image: the SSIM the CLI reports (BasicSR's calculate_ssim, 11-tap
+        Gaussian window, per channel) on the unrounded images — on the composite where ``loss_region`` selects one; ``last_loss_terms['ssim']`` is
+        its table (None when off).  A negative or non-finite weight raises ValueError.
         ``streams`` (opt-in; ``bench.py`` uses 2, the CLI's ``inversion.streams`` sets it): the W+ loop advances the batch as
         that many independent sub-batches on concurrent HIP streams (images are independent; the HBM-bound layout
         kernels of one sub-batch run beside the matrix kernels of the other: +4 % at batch 8).  The
@@ -282,6 +285,7 @@ class ood_faceGAN_e4e(nn.Module):
         same ``noise`` — the error of the blended output this method returns, with the mask frozen for the run.  A float32 (B,1,S,S) tensor
         in [0,1] on the model's device: that beta (a caller mask: 0 = ignore the pixel).  ``self.last_loss_weight`` is the beta optimised
         (None for 'full')."""
+        ssim_weight = check_ssim_weight(ssim_weight)
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
         if noise is None:
@@ -299,7 +303,7 @@ class ood_faceGAN_e4e(nn.Module):
                 st = lpips_state if lpips_state is not None else _seeded(0)
                 self._lpips_net, self._lpips_key = LPIPSAlex({k: v.to(x.device) for k, v in st.items()}, min_max=(-1.0, 1.0)), key
             lp = self._lpips_net
-        inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight)
+        inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise')}

@@ -19,6 +19,9 @@ Where the W+ loss looks, in the same block:
     mask_dir: <dir>              a caller mask per input file: <dir>/<base name>.png (grayscale; the first channel / 255 is beta,
                                  0 = ignore the pixel), resized nearest to the generator size.  A file without a mask is an error.
                                  Excludes ``loss_region: blend``.
+    ssim_weight: <lambda>        adds lambda * (1 - SSIM) per image to the W+ loss: the SSIM this tool reports (11-tap Gaussian
+                                 window, per channel), on the unrounded images, of the composite where a region is set.  Default 0 = off;
+                                 negative or non-finite is an error.
 ``model_dict`` holds the reference's three variants (run_ood_faceGAN_inversion.py:23-27): the ``network_g`` blocks of
 options/test/{E4E,ReStyle,FeatureStyle}_Face_test.yml resolve unchanged.  LPIPS / identity need third-party weights that
 do not ship: they are reported as skipped."""
@@ -33,6 +36,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
+from .engine import check_ssim_weight
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -115,6 +119,7 @@ def run(opts, wplus_steps=None, log=None):
         raise ValueError(f"inversion.loss_region must be 'full' or 'blend', got {loss_region!r}")
     if mask_dir and loss_region != 'full':
         raise ValueError('inversion.mask_dir and inversion.loss_region: blend exclude each other')
+    ssim_weight = check_ssim_weight(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
     model = load_model(opts).cuda().eval()
@@ -151,7 +156,7 @@ def run(opts, wplus_steps=None, log=None):
                 t0 = time.time()
                 if steps > 0:
                     out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
-                                       loss_region=region)[0]
+                                       loss_region=region, ssim_weight=ssim_weight)[0]
                 else:
                     out = (graphed(x) if graphed is not None else model(x))[0]
                 torch.cuda.synchronize()

@@ -781,6 +781,8 @@ class _WRun:
         self.lp = inv.lpips if (inv.lpips is not None and inv.lpips_weight != 0.0) else None
         self.lp_target = self.lp.target_taps(target) if self.lp is not None else None
         self.lp_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if self.lp is not None else None
+        # optional SSIM term (csrc/loss_ssim.hip): a third loss table, 1 - SSIM per step and image
+        self.ss_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.ssim_weight != 0.0 else None
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0
@@ -816,31 +818,46 @@ class _WRun:
             _, gimg = ops.mse_loss_grad(img, self.target, self.gmul, table=self.lbuf, row_dev=self.dev_t)
             if self.lp is not None:     # gimg += gmul * lambda * d(sum_b lpips_b)/d(img); values to row t of the second table
                 self.lp.loss_and_grad(img, gimg, inv.lpips_weight * self.gmul, table=self.lp_table, row_dev=self.dev_t, target_taps=self.lp_target)
+            self._ssim_term(img, gimg)
             g = eng.backward(gimg, self.gmul, carry_scale=True)
             ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
         else:
             _, gimg = ops.mse_loss_grad(img, self.target, self.gmul, loss_out=self.lbuf[self.t])
             if self.lp is not None:
                 self.lp_table[self.t].copy_(self.lp.loss_and_grad(img, gimg, inv.lpips_weight * self.gmul, target_taps=self.lp_target))
+            self._ssim_term(img, gimg)
             g = eng.backward(gimg, self.gmul, carry_scale=True)
             ops.adam_step(self.w, g, self.m, self.v, self.t + 1, inv.lr, inv.betas, inv.eps)
 
-    def _masked_loss(self, img):
-        """The composite loss of the step and its gradient w.r.t. the generator output.  Without LPIPS one kernel writes beta*dL/dc; with it the
-        kernel writes dL/dc and the composite c, LPIPS(c, x) adds its part of dL/dc, and beta is applied once afterwards."""
-        inv, lp = self.inv, self.lp
-        wrt = 'gen' if lp is None else 'composite'
+    def _ssim_term(self, img, gimg):
+        """gimg += gmul * ssim_weight * d(sum_b (1 - SSIM_b))/d(img); the values to row t of the third table (the device counter's row in a
+        recorded step; a rolled-back window simply rewrites its rows)."""
+        if self.ss_table is None:
+            return
         if self.dev_t is not None:
-            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=lp is not None,
+            ops.ssim_loss_grad(img, self.target, gimg, self.inv.ssim_weight * self.gmul, table=self.ss_table, row_dev=self.dev_t)
+        else:
+            ops.ssim_loss_grad(img, self.target, gimg, self.inv.ssim_weight * self.gmul, loss_out=self.ss_table[self.t])
+
+    def _masked_loss(self, img):
+        """The composite loss of the step and its gradient w.r.t. the generator output.  Without LPIPS and SSIM one kernel writes beta*dL/dc;
+        with either the kernel writes dL/dc and the composite c, LPIPS(c, x) and 1 - SSIM(c, x) add their parts of dL/dc, and beta is applied
+        once afterwards."""
+        inv, lp = self.inv, self.lp
+        on_c = lp is not None or self.ss_table is not None
+        wrt = 'composite' if on_c else 'gen'
+        if self.dev_t is not None:
+            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=on_c,
                                                         table=self.lbuf, row_dev=self.dev_t)
             if lp is not None:
                 lp.loss_and_grad(comp, gimg, inv.lpips_weight * self.gmul, table=self.lp_table, row_dev=self.dev_t, target_taps=self.lp_target)
         else:
-            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=lp is not None,
+            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=on_c,
                                                         loss_out=self.lbuf[self.t])
             if lp is not None:
                 self.lp_table[self.t].copy_(lp.loss_and_grad(comp, gimg, inv.lpips_weight * self.gmul, target_taps=self.lp_target))
-        if lp is not None:
+        if on_c:
+            self._ssim_term(comp, gimg)
             ops.scale_by_plane(gimg, self.beta)
         return gimg
 
@@ -953,6 +970,17 @@ class _WRun:
         self.pool = None
 
 
+def check_ssim_weight(value, name='ssim_weight'):
+    """The weight of the SSIM loss term as a float; ValueError unless it is a finite number >= 0."""
+    try:
+        w = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f'{name} must be a finite number >= 0, got {value!r}') from None
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f'{name} must be a finite number >= 0, got {value!r}')
+    return w
+
+
 class WPlusInverter:
     """Build-defined W+ optimisation loop: ``steps`` x {G(w) with fixed noise,
     per-image MSE, backward to w, Adam(lr, betas, eps)} — anchors: reference Generator.forward with
@@ -962,12 +990,16 @@ class WPlusInverter:
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}."""
 
-    def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0):
+    def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
+                 ssim_weight=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
         # loss = per-image MSE + lpips_weight * LPIPS(alex) (north_star: "W+ Adam steps against LPIPS/L2"); ``lpips``: an oodgan.lpips.LPIPSAlex
         # (min_max = the generator's output range).  Off by default: the `lpips` weights are third-party and absent here (parity unpinned).
-        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'mse', 'lpips'} tables.
+        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'mse', 'lpips', 'ssim'} tables (None: term off).
         self.lpips, self.lpips_weight = lpips, float(lpips_weight)
+        # + ssim_weight * (1 - SSIM) (DESIGN.md §15): the metric the CLI reports, on the unrounded images; 0 (default) = the term, its
+        # kernel launches and its table do not exist
+        self.ssim_weight = check_ssim_weight(ssim_weight)
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; the single-stream loop uses the device step counter with them
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
@@ -1064,7 +1096,7 @@ class WPlusInverter:
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         if streams == 1:
             r = runs[0]
-            losses = self._total(r.lbuf, r.lp_table)
+            losses = self._total(r.lbuf, r.lp_table, r.ss_table)
             return (r.w, losses, r.traj) if return_trajectory else (r.w, losses)
         cur = torch.cuda.current_stream()
         for st in side:
@@ -1072,16 +1104,20 @@ class WPlusInverter:
         w = torch.cat([r.w for r in runs], 0)
         losses = torch.cat([r.lbuf for r in runs], 1)
         lp = torch.cat([r.lp_table for r in runs], 1) if runs[0].lp_table is not None else None
+        ss = torch.cat([r.ss_table for r in runs], 1) if runs[0].ss_table is not None else None
         for r in runs:                      # tensors produced on side streams are consumed on the caller's stream
             r.w.record_stream(cur)
             r.lbuf.record_stream(cur)
             if r.lp_table is not None:
                 r.lp_table.record_stream(cur)
-        return w, self._total(losses, lp)
+            if r.ss_table is not None:
+                r.ss_table.record_stream(cur)
+        return w, self._total(losses, lp, ss)
 
-    def _total(self, mse, lp):
-        self.last_terms = {'mse': mse, 'lpips': lp}
-        return mse if lp is None else mse + self.lpips_weight * lp
+    def _total(self, mse, lp, ss=None):
+        self.last_terms = {'mse': mse, 'lpips': lp, 'ssim': ss}
+        total = mse if lp is None else mse + self.lpips_weight * lp
+        return total if ss is None else total + self.ssim_weight * ss
 
     def _invert_graph(self, target, w0, noises, steps, streams):
         """hipGraph replay of one captured W+ step per stream (measured 3 % slower than eager launches on this host; kept as an
@@ -1089,6 +1125,8 @@ class WPlusInverter:
         repeated eagerly (with the per-window guard)."""
         if self.lpips is not None and self.lpips_weight != 0.0:
             raise NotImplementedError('use_graph with the LPIPS term: use the launch plans (default) instead')
+        if self.ssim_weight != 0.0:
+            raise NotImplementedError('use_graph with the SSIM term: use the launch plans (default) instead')
         B = w0.shape[0]
         cur = torch.cuda.current_stream()
         side = _side_streams(w0.device, streams)

@@ -1275,6 +1275,31 @@ def scale_by_plane(g, beta):
     return g
 
 
+def ssim_loss_grad(img, target, gimg=None, grad_mul=1.0, loss_out=None, table=None, row_dev=None):
+    """The SSIM term (oodgan_ssim_loss_fwd_bwd): per-image 1 - SSIM(img, target) for (B,C,H,W) float32 images in [-1,1], H, W >= 11
+    (``imgio.calculate_ssim`` on the unrounded 127.5*(x+1) images).  ``gimg`` (B,C,H,W), contiguous: gimg += grad_mul * d(sum_b (1 - SSIM_b))/d(img),
+    accumulated into what ``mse_loss_grad`` wrote (as ``LPIPSAlex.loss_and_grad``); None: forward only, the same value bit for bit.  Returns
+    (1 - SSIM)[B], or None with ``table``; ``loss_out`` / ``table`` + ``row_dev``: as ``mse_loss_grad``."""
+    a, t = _dev(img, 'img'), _dev(target, 'target')
+    if a.dim() != 4 or a.shape != t.shape:
+        raise ValueError(f'ssim_loss_grad: img and target must be (B,C,H,W) of one shape, got {tuple(a.shape)} and {tuple(t.shape)}')
+    B, C, H, W = a.shape
+    if gimg is not None:
+        assert gimg.shape == a.shape and gimg.dtype == torch.float32 and gimg.is_contiguous() and gimg.device == a.device, \
+            'ssim_loss_grad: gimg must be a contiguous float32 tensor of the image\'s shape (it is updated in place)'
+    L = _lib.lib()
+    part = torch.empty(B, L.oodgan_ssim_nparts(C, H, W), device=a.device, dtype=torch.float32)
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and row_dev.dtype == torch.int32
+        check(L.oodgan_ssim_loss_fwd_bwd_row(_p(a), _p(t), _p(gimg), _p(part), _p(table), _p(row_dev), table.shape[0], B, C, H, W, float(grad_mul),
+                                             _stream()), 'ssim_loss_row')
+        return None
+    loss = torch.empty(B, device=a.device, dtype=torch.float32) if loss_out is None else loss_out
+    assert loss.shape == (B,) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == a.device
+    check(L.oodgan_ssim_loss_fwd_bwd(_p(a), _p(t), _p(gimg), _p(part), _p(loss), B, C, H, W, float(grad_mul), _stream()), 'ssim_loss')
+    return loss
+
+
 def loss_weight_from_alpha(alpha, power=1):
     """beta = clip(1 - alpha, 0, 1)^power (oodgan_loss_weight_from_alpha): the loss weight of the composite that ``blend`` applied ``power`` times
     produces from the mask ``alpha`` (B,1,S,S) of ``blending_mask``."""
