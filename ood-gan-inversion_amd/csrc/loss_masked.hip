@@ -5,14 +5,12 @@
 //   scale_by_plane: g <- beta (.) g (the chain rule from c to G once LPIPS has accumulated into the gradient w.r.t. c);
 //   loss_weight_from_alpha: beta = clip(1 - alpha, 0, 1)^n (the composite that `blend` applied n times produces).
 // With beta == 1 the loss and the gradient are bit-identical to oodgan_mse_fwd_bwd: the same chunks of kMseChunk elements per block,
-// the same float4 order per thread, the same two-stage sums (block_sum_256, then one wave over the partials); no float atomics.
-#include "common.hpp"
+// the same float4 order per thread, the same two-stage sums (block_sum_256, then mean_finish_kernel's one wave over the partials); no float atomics.
+#include "loss_common.hpp"
 
 using namespace oodgan;
 
 namespace {
-
-constexpr int kMseChunk = 16384;        // = kMseChunk of elementwise.hip (checked against oodgan_mse_nparts at every call)
 
 // Plane form (HW a multiple of kMseChunk): block j of image b owns pixel chunk j of ALL C channel planes — beta is read once per
 // pixel and used for every channel — and keeps one accumulator per channel, so that the partial sum of channel chunk c*HW/kMseChunk + j
@@ -101,17 +99,6 @@ __global__ __launch_bounds__(256) void composite_mse_flat_kernel(const float* __
     if (threadIdx.x == 0) part[(long)b * nparts + blockIdx.x] = acc;
 }
 
-// = mse_finish_kernel of elementwise.hip (the same order over the partials); row_dev != NULL: row min(row_dev[0], nrows-1) of the loss table
-__global__ __launch_bounds__(64) void composite_mse_finish_kernel(const float* __restrict__ part, float* __restrict__ loss, int nparts,
-                                                                  float inv_n, const int* __restrict__ row_dev, int nrows) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float s = 0.f;
-    for (int j = lane; j < nparts; j += 64) s += part[(long)b * nparts + j];
-    s = wave_sum(s);
-    const long row = row_dev ? (long)min(max(row_dev[0], 0), nrows - 1) * gridDim.x : 0;
-    if (lane == 0) loss[row + b] = s * inv_n;
-}
-
 // g[b, c, p] *= beta[b, p]: one thread per pixel (four with float4), beta read once for the C channels
 __global__ __launch_bounds__(256) void scale_by_plane_kernel(float* __restrict__ g, const float* __restrict__ beta, int C, long HW, long npix) {
     const long stride = (long)gridDim.x * blockDim.x;
@@ -155,7 +142,6 @@ int composite_mse(const float* img, const float* target, const float* beta, floa
                   const int* row_dev, int nrows, int B, int C, long HW, int wrt_gen, float grad_mul, void* stream) {
     const long CHW = (long)C * HW;
     const int nparts = oodgan_mse_nparts(CHW);
-    OODGAN_REQUIRE(nparts == (int)((CHW + kMseChunk - 1) / kMseChunk), "composite_mse: chunking differs from oodgan_mse_nparts");
     const float gscale = grad_mul * 2.0f / (float)CHW;
     count_dispatch(OODGAN_DC_COMPOSITE_MSE);
     if (C == 3 && HW % kMseChunk == 0) {
@@ -167,8 +153,7 @@ int composite_mse(const float* img, const float* target, const float* beta, floa
     }
     int rc = check_launch("composite_mse");
     if (rc != OODGAN_OK) return rc;
-    hipLaunchKernelGGL(composite_mse_finish_kernel, dim3(B), dim3(64), 0, as_stream(stream), part, loss, nparts, 1.0f / (float)CHW, row_dev,
-                       row_dev ? nrows : 1);
+    hipLaunchKernelGGL(mean_finish_kernel<>, dim3(B), dim3(64), 0, as_stream(stream), part, loss, nparts, 1.0f / (float)CHW, row_dev, nrows);
     return check_launch("composite_mse_finish");
 }
 

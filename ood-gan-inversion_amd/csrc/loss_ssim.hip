@@ -14,7 +14,7 @@
 // The forward-only mode (gimg NULL) is the same kernel without FH/FV, so its value is the fwd+bwd value bit for bit.  Sums: one
 // partial per block (block_sum_256), then one wave per image over the partials in float64 — deterministic, no float atomics.
 // Bytes per image at 1024²: G and x read (25 MB, the halo comes from L2), gimg read + written (25 MB).
-#include "common.hpp"
+#include "loss_common.hpp"
 
 #include <cmath>
 
@@ -186,14 +186,14 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
     return v;
 }
 
-// loss[b] = 1 - (sum of the image's partials) / n; row_dev != NULL: row min(row_dev[0], nrows-1) of the loss table
+// loss[row + b] = 1 - (sum of the image's partials) / n, the sum in float64; the row: loss_row
 __global__ __launch_bounds__(64) void ssim_finish_kernel(const float* __restrict__ part, float* __restrict__ loss, int nparts, double inv_n,
                                                          const int* __restrict__ row_dev, int nrows) {
     const int b = blockIdx.x, lane = threadIdx.x;
     double s = 0.0;
     for (int j = lane; j < nparts; j += 64) s += (double)part[(long)b * nparts + j];
     s = wave_sum_f64(s);
-    const long row = row_dev ? (long)min(max(row_dev[0], 0), nrows - 1) * gridDim.x : 0;
+    const long row = loss_row(row_dev, nrows, gridDim.x);
     if (lane == 0) loss[row + b] = (float)(1.0 - s * inv_n);
 }
 
@@ -216,8 +216,7 @@ int ssim_loss(const float* img, const float* target, float* gimg, float* part, f
                        (float)(-(double)grad_mul / n), taps);
     int rc = check_launch("ssim_fused");
     if (rc != OODGAN_OK) return rc;
-    hipLaunchKernelGGL(ssim_finish_kernel, dim3(B), dim3(64), 0, as_stream(stream), part, loss, C * ty * tx, 1.0 / n, row_dev,
-                       row_dev ? nrows : 1);
+    hipLaunchKernelGGL(ssim_finish_kernel, dim3(B), dim3(64), 0, as_stream(stream), part, loss, C * ty * tx, 1.0 / n, row_dev, nrows);
     return check_launch("ssim_finish");
 }
 

@@ -15,6 +15,7 @@
 // staged through LDS with the next chunk's global loads in flight under the matrix loop.  Epilogue: + bias, ReLU (forward) or
 // + add, x (mask > 0) (backward: the tap's own gradient joins the back-propagated one, then the ReLU below).
 #include "conv_common.hpp"
+#include "loss_common.hpp"
 #include <cstdint>
 
 using namespace oodgan;
@@ -367,7 +368,7 @@ struct FinishArgs {
     float inv_hw[5];
     int ntaps;
 };
-// lpips[b] = sum_taps (sum_blocks part) / HW_tap  -> row min(row_dev[0], nrows-1) of table (nrows, B) (row_dev NULL: row 0)
+// lpips[b] = sum_taps (sum_blocks part) / HW_tap  -> table[loss_row + b]
 __global__ __launch_bounds__(64) void lpips_finish_kernel(const FinishArgs a, float* __restrict__ table, const int* __restrict__ row_dev,
                                                           int nrows) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -377,7 +378,7 @@ __global__ __launch_bounds__(64) void lpips_finish_kernel(const FinishArgs a, fl
         for (int j = lane; j < a.nparts[t]; j += 64) s += a.part[t][(long)b * a.nparts[t] + j];
         tot += wave_sum(s) * a.inv_hw[t];
     }
-    const long row = row_dev ? (long)min(max(row_dev[0], 0), nrows - 1) * gridDim.x : 0;
+    const long row = loss_row(row_dev, nrows, gridDim.x);
     if (lane == 0) table[row + b] = tot;
 }
 

@@ -755,7 +755,9 @@ def _flag_stream(device):
 
 
 class _WRun:
-    """One (sub-)batch of the W+ loop on one HIP stream, advanced one step per ``advance()``.
+    """One (sub-)batch of the W+ loop on one HIP stream, advanced one step per ``advance()``.  A step is forward, ``_loss_grad`` (the one
+    place that knows the loss terms), backward, Adam; its step index lives on the device (``dev_t``), so every step — driven from Python or
+    replayed from a launch plan — is the same launch list.
 
     Range guard (round 6): the carried forward / backward range scales raise sticky device flags when a tensor's range
     moved by more than the format's head-room within one step (range control).  Until round 5 the flags were read after the last
@@ -765,7 +767,7 @@ class _WRun:
     snapshot becomes the last clean state.  Set: the run goes back to the last clean state, repeats that window (<= check_every steps)
     with exact scales, and continues in carry mode from freshly measured scales."""
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, dev_counter, keep_traj, beta=None):
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, beta=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -774,8 +776,10 @@ class _WRun:
         self.w = w0.detach().clone().contiguous()
         self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
         self.gmul = ops.loss_scale_for(target.numel() // target.shape[0])
+        # the step index twice: ``t`` for the host's control flow, ``dev_t`` on the device for the step's kernels — the row of the loss tables
+        # and Adam's bias corrections — so that a step is the same launch list for every t, recorded or driven from Python
         self.t = 0
-        self.dev_t = torch.zeros(1, dtype=torch.int32, device=self.w.device) if dev_counter else None
+        self.dev_t = torch.zeros(1, dtype=torch.int32, device=self.w.device)
         self.lbuf = torch.empty(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32)
         # optional LPIPS(alex) term (oodgan/lpips.py): the target's normalised taps once, a second loss table
         self.lp = inv.lpips if (inv.lpips is not None and inv.lpips_weight != 0.0) else None
@@ -799,65 +803,35 @@ class _WRun:
         # included (seen as NaN from the second replay on).  The third step is RECORDED while it runs (oodgan_plan_*, under a private
         # allocator pool so that every buffer it touched keeps its address); every later step is one oodgan_plan_run call instead of ~100
         # ctypes calls and the Python between them
-        self.use_plan = bool(inv.use_plan) and dev_counter and not keep_traj and eng.sform
+        self.use_plan = bool(inv.use_plan) and not keep_traj and eng.sform     # the trajectory's per-step w.clone() is a torch kernel outside the plan
         self.plan, self.pool, self.eager_left, self.plan_steps, self.plan_size = None, None, 2, 0, 0
 
     # ---- one W+ step on the current stream
     def _eager_step(self):
         eng, inv = self.eng, self.inv
         img = eng.forward(self.w, self.noises, save=True, range_mode='carry')
-        if self.beta is not None:
-            gimg = self._masked_loss(img)
-            g = eng.backward(gimg, self.gmul, carry_scale=True)
-            if self.dev_t is not None:
-                ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
-            else:
-                ops.adam_step(self.w, g, self.m, self.v, self.t + 1, inv.lr, inv.betas, inv.eps)
-        elif self.dev_t is not None:
-            # loss row and Adam's step index from the device counter: the recorded step is the same launch list for every t
-            _, gimg = ops.mse_loss_grad(img, self.target, self.gmul, table=self.lbuf, row_dev=self.dev_t)
-            if self.lp is not None:     # gimg += gmul * lambda * d(sum_b lpips_b)/d(img); values to row t of the second table
-                self.lp.loss_and_grad(img, gimg, inv.lpips_weight * self.gmul, table=self.lp_table, row_dev=self.dev_t, target_taps=self.lp_target)
-            self._ssim_term(img, gimg)
-            g = eng.backward(gimg, self.gmul, carry_scale=True)
-            ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
-        else:
-            _, gimg = ops.mse_loss_grad(img, self.target, self.gmul, loss_out=self.lbuf[self.t])
-            if self.lp is not None:
-                self.lp_table[self.t].copy_(self.lp.loss_and_grad(img, gimg, inv.lpips_weight * self.gmul, target_taps=self.lp_target))
-            self._ssim_term(img, gimg)
-            g = eng.backward(gimg, self.gmul, carry_scale=True)
-            ops.adam_step(self.w, g, self.m, self.v, self.t + 1, inv.lr, inv.betas, inv.eps)
+        gimg = self._loss_grad(img)
+        g = eng.backward(gimg, self.gmul, carry_scale=True)
+        ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
 
-    def _ssim_term(self, img, gimg):
-        """gimg += gmul * ssim_weight * d(sum_b (1 - SSIM_b))/d(img); the values to row t of the third table (the device counter's row in a
-        recorded step; a rolled-back window simply rewrites its rows)."""
-        if self.ss_table is None:
-            return
-        if self.dev_t is not None:
-            ops.ssim_loss_grad(img, self.target, gimg, self.inv.ssim_weight * self.gmul, table=self.ss_table, row_dev=self.dev_t)
+    def _loss_grad(self, img):
+        """The loss of the step, each term's values to row dev_t of its table, and gmul * d(sum_b loss_b)/d(img).  The terms in the order
+        they accumulate into the gradient: the MSE writes it, LPIPS and 1 - SSIM add lambda * gmul * their part.  With a loss weight beta
+        the terms are taken on the composite c: alone, the composite MSE writes beta*dL/dc in one kernel; with LPIPS or
+        SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards."""
+        inv, gmul, row = self.inv, self.gmul, self.dev_t
+        on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
+        if self.beta is None:
+            _, gimg = ops.mse_loss_grad(img, self.target, gmul, table=self.lbuf, row_dev=row)
         else:
-            ops.ssim_loss_grad(img, self.target, gimg, self.inv.ssim_weight * self.gmul, loss_out=self.ss_table[self.t])
-
-    def _masked_loss(self, img):
-        """The composite loss of the step and its gradient w.r.t. the generator output.  Without LPIPS and SSIM one kernel writes beta*dL/dc;
-        with either the kernel writes dL/dc and the composite c, LPIPS(c, x) and 1 - SSIM(c, x) add their parts of dL/dc, and beta is applied
-        once afterwards."""
-        inv, lp = self.inv, self.lp
-        on_c = lp is not None or self.ss_table is not None
-        wrt = 'composite' if on_c else 'gen'
-        if self.dev_t is not None:
-            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=on_c,
-                                                        table=self.lbuf, row_dev=self.dev_t)
-            if lp is not None:
-                lp.loss_and_grad(comp, gimg, inv.lpips_weight * self.gmul, table=self.lp_table, row_dev=self.dev_t, target_taps=self.lp_target)
-        else:
-            _, gimg, comp = ops.composite_mse_loss_grad(img, self.target, self.beta, self.gmul, wrt=wrt, composite=on_c,
-                                                        loss_out=self.lbuf[self.t])
-            if lp is not None:
-                self.lp_table[self.t].copy_(lp.loss_and_grad(comp, gimg, inv.lpips_weight * self.gmul, target_taps=self.lp_target))
+            _, gimg, c = ops.composite_mse_loss_grad(img, self.target, self.beta, gmul, wrt='composite' if on_c else 'gen', composite=on_c,
+                                                     table=self.lbuf, row_dev=row)
+        x = c if on_c else img
+        if self.lp is not None:
+            self.lp.loss_and_grad(x, gimg, inv.lpips_weight * gmul, table=self.lp_table, row_dev=row, target_taps=self.lp_target)
+        if self.ss_table is not None:
+            ops.ssim_loss_grad(x, self.target, gimg, inv.ssim_weight * gmul, table=self.ss_table, row_dev=row)
         if on_c:
-            self._ssim_term(comp, gimg)
             ops.scale_by_plane(gimg, self.beta)
         return gimg
 
@@ -917,8 +891,7 @@ class _WRun:
             self.m.copy_(m)
             self.v.copy_(v)
         self.t = t0
-        if self.dev_t is not None:
-            self.dev_t.fill_(t0)
+        self.dev_t.fill_(t0)
         self.rollbacks += 1
         self.plan = None                                         # the carried state it points to is rebuilt: recorded again after the window
         eng.fused_bwd = eng.carry_range = False                  # exact per-step scales, both directions, for the flagged window
@@ -987,6 +960,9 @@ class WPlusInverter:
     ``noise=<list>`` (model.py:483-585), torch.optim.Adam as built by get_optimizer
     (src/models/OOD_faceGAN_model.py:398-400), basicsr MSELoss (losses.py:58-83).
 
+    The loss of a step is defined once, in ``_WRun._loss_grad``: MSE (or the composite MSE with a loss weight) + lpips_weight * LPIPS +
+    ssim_weight * (1 - SSIM); the step index is a device counter in every mode (plan, Python-driven, trajectory, any number of streams).
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}."""
 
@@ -1001,7 +977,7 @@ class WPlusInverter:
         # kernel launches and its table do not exist
         self.ssim_weight = check_ssim_weight(ssim_weight)
         self.last_terms = None
-        # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; the single-stream loop uses the device step counter with them
+        # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
         self.check_every, self.check_lag = int(check_every), max(0, int(check_lag))
         self._runs, self._pins = [], []
@@ -1053,36 +1029,54 @@ class WPlusInverter:
             if override:
                 _lib.set_tunable('s1_big_min_items', old)
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, beta=None):
+    def _split(self, target, w0, noises, beta, streams):
+        """(side streams, engines, [(target, w0, noises, beta)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams)."""
         B = w0.shape[0]
+        cur = torch.cuda.current_stream()
+        side = _side_streams(w0.device, streams)
+        # the state resets enqueue zero-fills on the CALLER's stream: they must precede the wait_stream below, or nothing
+        # orders them against the atomicOr / atomic max the side streams do on the same flags (engines[0] keeps its
+        # FwdRange and bwd_flag across calls)
+        engines = [self.engine] + [self.engine.clone_shared() for _ in range(streams - 1)]
+        for eng in engines:
+            eng.reset_bwd_state()
+            eng.reset_fwd_state()
+        parts = []
+        for i in range(streams):
+            sl = slice((i * B) // streams, ((i + 1) * B) // streams)
+            parts.append((target[sl].contiguous(), w0[sl].detach().contiguous(),
+                          [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous()))
+        for st in side:
+            st.wait_stream(cur)                 # AFTER the slices above were enqueued on the caller's stream
+        return side, engines, parts
+
+    @staticmethod
+    def _gather(side, w, tables):
+        """The per-stream latents (joined along the batch) and loss tables (``tables``: one list per term, None = term off; joined along the
+        images) on the caller's stream."""
+        cur = torch.cuda.current_stream()
+        for st in side:
+            cur.wait_stream(st)
+        out = [torch.cat(w, 0)] + [None if ts[0] is None else torch.cat(ts, 1) for ts in tables]
+        for ts in [w] + tables:                 # tensors produced on side streams are consumed on the caller's stream
+            for t in ts:
+                if t is not None:
+                    t.record_stream(cur)
+        return out
+
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, beta=None):
         self._runs = []
         if streams == 1:
             eng = self.engine
             eng.reset_bwd_state()
             eng.reset_fwd_state()
-            runs = [_WRun(self, eng, target, w0, noises, steps, None, self.use_plan and not return_trajectory, return_trajectory, beta)]
+            runs = [_WRun(self, eng, target, w0, noises, steps, None, return_trajectory, beta)]
         else:
-            cur = torch.cuda.current_stream()
-            side = _side_streams(w0.device, streams)
-            # the state resets enqueue zero-fills on the CALLER's stream: they must precede the wait_stream below, or nothing
-            # orders them against the atomicOr / atomic max the side streams do on the same flags (engines[0] keeps its
-            # FwdRange and bwd_flag across calls)
-            engines = [self.engine] + [self.engine.clone_shared() for _ in range(streams - 1)]
-            for eng in engines:
-                eng.reset_bwd_state()
-                eng.reset_fwd_state()
-            cuts = [(i * B) // streams for i in range(streams + 1)]
-            parts = []
-            for i in range(streams):
-                sl = slice(cuts[i], cuts[i + 1])
-                parts.append((target[sl].contiguous(), w0[sl].detach().contiguous(),
-                              [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous()))
-            for st in side:
-                st.wait_stream(cur)                 # AFTER the slices above were enqueued on the caller's stream
+            side, engines, parts = self._split(target, w0, noises, beta, streams)
             runs = []
             for i, st in enumerate(side):
                 with torch.cuda.stream(st):         # state tensors initialised on the stream that uses them
-                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, True, False, parts[i][3]))
+                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, False, parts[i][3]))
         try:
             busy = True
             while busy:
@@ -1098,21 +1092,8 @@ class WPlusInverter:
             r = runs[0]
             losses = self._total(r.lbuf, r.lp_table, r.ss_table)
             return (r.w, losses, r.traj) if return_trajectory else (r.w, losses)
-        cur = torch.cuda.current_stream()
-        for st in side:
-            cur.wait_stream(st)
-        w = torch.cat([r.w for r in runs], 0)
-        losses = torch.cat([r.lbuf for r in runs], 1)
-        lp = torch.cat([r.lp_table for r in runs], 1) if runs[0].lp_table is not None else None
-        ss = torch.cat([r.ss_table for r in runs], 1) if runs[0].ss_table is not None else None
-        for r in runs:                      # tensors produced on side streams are consumed on the caller's stream
-            r.w.record_stream(cur)
-            r.lbuf.record_stream(cur)
-            if r.lp_table is not None:
-                r.lp_table.record_stream(cur)
-            if r.ss_table is not None:
-                r.ss_table.record_stream(cur)
-        return w, self._total(losses, lp, ss)
+        w, mse, lp, ss = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs]])
+        return w, self._total(mse, lp, ss)
 
     def _total(self, mse, lp, ss=None):
         self.last_terms = {'mse': mse, 'lpips': lp, 'ssim': ss}
@@ -1127,25 +1108,16 @@ class WPlusInverter:
             raise NotImplementedError('use_graph with the LPIPS term: use the launch plans (default) instead')
         if self.ssim_weight != 0.0:
             raise NotImplementedError('use_graph with the SSIM term: use the launch plans (default) instead')
-        B = w0.shape[0]
-        cur = torch.cuda.current_stream()
-        side = _side_streams(w0.device, streams)
-        engines = [self.engine] + [self.engine.clone_shared() for _ in range(streams - 1)]
-        for eng in engines:
-            eng.reset_bwd_state()
-            eng.reset_fwd_state()
-        cuts = [(i * B) // streams for i in range(streams + 1)]
+        side, engines, split = self._split(target, w0, noises, None, streams)
+        gmul = ops.loss_scale_for(target.numel() // w0.shape[0])
+        dev = w0.device
         parts = []
         for i, st in enumerate(side):
-            sl = slice(cuts[i], cuts[i + 1])
-            parts.append(dict(target=target[sl].contiguous(), w=w0[sl].detach().clone().contiguous(),
-                              noises=[n[sl].contiguous() if n.shape[0] == B else n for n in noises]))
-            parts[-1]['m'] = torch.zeros_like(parts[-1]['w'])
-            parts[-1]['v'] = torch.zeros_like(parts[-1]['w'])
-        for st in side:
-            st.wait_stream(cur)
-        gmul = ops.loss_scale_for(target.numel() // B)
-        dev = w0.device
+            with torch.cuda.stream(st):             # state tensors initialised on the stream that uses them
+                w = split[i][1].clone()
+                parts.append(dict(target=split[i][0], w=w, noises=split[i][2], m=torch.zeros_like(w), v=torch.zeros_like(w),
+                                  t=torch.zeros(1, dtype=torch.int32, device=dev),
+                                  lbuf=torch.empty(steps, w.shape[0], device=dev, dtype=torch.float32)))
 
         def one_step(pr, eng):
             img = eng.forward(pr['w'], pr['noises'], save=True, range_mode='carry')
@@ -1154,11 +1126,6 @@ class WPlusInverter:
             ops.adam_step_dev(pr['w'], g, pr['m'], pr['v'], pr['t'], self.lr, self.betas, self.eps)
             return loss
 
-        for i, st in enumerate(side):
-            pr = parts[i]
-            with torch.cuda.stream(st):
-                pr['t'] = torch.zeros(1, dtype=torch.int32, device=dev)
-                pr['lbuf'] = torch.empty(steps, pr['w'].shape[0], device=dev, dtype=torch.float32)
         for i, st in enumerate(side):       # step 1 eagerly (also warms allocator pools / scratch buffers of every stream) ...
             with torch.cuda.stream(st):
                 parts[i]['lbuf'][0].copy_(one_step(parts[i], engines[i]))
@@ -1176,15 +1143,9 @@ class WPlusInverter:
                 with torch.cuda.stream(st):
                     graphs[i].replay()
                     parts[i]['lbuf'][t - 1].copy_(parts[i]['lstat'])
-        for st in side:
-            cur.wait_stream(st)
+        w, losses = self._gather(side, [pr['w'] for pr in parts], [[pr['lbuf'] for pr in parts]])
         for eng in engines:
             eng.saved = None
-        w = torch.cat([pr['w'] for pr in parts], 0)
-        losses = torch.cat([pr['lbuf'] for pr in parts], 1)
-        for pr in parts:
-            pr['w'].record_stream(cur)
-            pr['lbuf'].record_stream(cur)
         self._graphs = graphs               # keep the graphs (and their private pools) alive until the next call
         self.last_stats = {'steps_run': [steps] * streams, 'rollbacks': [0] * streams}
         if any(eng.bwd_scale_violated() or eng.fwd_range_violated() for eng in engines):

@@ -172,12 +172,8 @@ class LPIPSAlex:
         parr = (ctypes.c_void_p * n)(*[p.data_ptr() for p in parts])
         narr = (ctypes.c_int * n)(*[p.shape[1] for p in parts])
         harr = (ctypes.c_long * n)(*[t.shape[2] * t.shape[3] for t in f])
-        if table is None:
-            out = torch.empty(B, device=img.device, dtype=torch.float32)
-            check(L.oodgan_lpips_finish(parr, narr, harr, n, _p(out), None, 1, B, _stream()), 'lpips_finish')
-        else:
-            out = None
-            check(L.oodgan_lpips_finish(parr, narr, harr, n, _p(table), _p(row_dev), table.shape[0], B, _stream()), 'lpips_finish')
+        dst, row, nrows, _, out = ops._loss_sink(B, img.device, None, table, row_dev)      # one entry point: row_dev NULL = a plain (B,)
+        check(L.oodgan_lpips_finish(parr, narr, harr, n, _p(dst), _p(row), nrows, B, _stream()), 'lpips_finish')
         if gimg is not None:
             assert gimg.shape == img.shape and gimg.is_contiguous() and gimg.dtype == torch.float32
             # backward through the stack: at every tap the head's gradient joins the back-propagated one, then the ReLU mask of that tap

@@ -1208,25 +1208,33 @@ def loss_scale_for(chw):
     return float(2 ** max(0, int(math.floor(math.log2(max(chw, 2) / 2.0)))))
 
 
+def _loss_sink(B, device, loss_out, table, row_dev):
+    """Where a loss op writes its B per-image values: (destination, row_dev or None, nrows, use the `_row` entry point?, the tensor to return).
+    ``table`` (nrows, B) float32 + ``row_dev`` (int32[1] on the device): row row_dev[0] of the table, nothing to return; otherwise
+    ``loss_out`` (a contiguous float32 (B,) view) or a new (B,) tensor."""
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and row_dev.dtype == torch.int32
+        return table, row_dev, table.shape[0], True, None
+    loss = torch.empty(B, device=device, dtype=torch.float32) if loss_out is None else loss_out
+    assert loss.shape == (B,) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == device
+    return loss, None, 1, False, loss
+
+
 def mse_loss_grad(img, target, grad_mul=1.0, loss_out=None, table=None, row_dev=None):
-    """Per-image MSE and its gradient (times grad_mul): (loss[B], gimg).  ``loss_out``: a contiguous float32 (B,) view that receives the losses
-    (the W+ loop's row of its loss table: no copy kernel per step).  ``table`` (nrows, B) + ``row_dev`` (int32[1] on the device): the losses go
-    to row row_dev[0] of the table (oodgan_mse_fwd_bwd_row: a recorded step writes a new row on every replay); returns (None, gimg)."""
+    """Per-image MSE and its gradient (times grad_mul): (loss[B], gimg).  ``loss_out``: a contiguous float32 (B,) view that receives the losses.
+    ``table`` (nrows, B) + ``row_dev`` (int32[1] on the device): the losses go to row row_dev[0] of the table (oodgan_mse_fwd_bwd_row: the W+
+    loop's loss table, a recorded step writes a new row on every replay); returns (None, gimg)."""
     a, t = _dev(img, 'img'), _dev(target, 'target')
     B = a.shape[0]
     CHW = a.numel() // B
     L = _lib.lib()
-    npart = L.oodgan_mse_nparts(CHW)
-    part = torch.empty(B, npart, device=a.device, dtype=torch.float32)
-    if table is not None:
-        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and row_dev.dtype == torch.int32
-        g = torch.empty_like(a)
-        check(L.oodgan_mse_fwd_bwd_row(_p(a), _p(t), _p(g), _p(part), _p(table), _p(row_dev), table.shape[0], B, CHW, float(grad_mul), _stream()), 'mse_row')
-        return None, g
-    loss = torch.empty(B, device=a.device, dtype=torch.float32) if loss_out is None else loss_out
-    assert loss.shape == (B,) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == a.device
+    part = torch.empty(B, L.oodgan_mse_nparts(CHW), device=a.device, dtype=torch.float32)
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
     g = torch.empty_like(a)
-    check(L.oodgan_mse_fwd_bwd(_p(a), _p(t), _p(g), _p(part), _p(loss), B, CHW, float(grad_mul), _stream()), 'mse')
+    if by_row:
+        check(L.oodgan_mse_fwd_bwd_row(_p(a), _p(t), _p(g), _p(part), _p(dst), _p(row), nrows, B, CHW, float(grad_mul), _stream()), 'mse_row')
+    else:
+        check(L.oodgan_mse_fwd_bwd(_p(a), _p(t), _p(g), _p(part), _p(dst), B, CHW, float(grad_mul), _stream()), 'mse')
     return loss, g
 
 
@@ -1254,15 +1262,13 @@ def composite_mse_loss_grad(img, target, beta, grad_mul=1.0, wrt='gen', composit
     g = torch.empty_like(a)
     c = torch.empty_like(a) if composite else None
     gen = 1 if wrt == 'gen' else 0
-    if table is not None:
-        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and row_dev.dtype == torch.int32
-        check(L.oodgan_composite_mse_fwd_bwd_row(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(table), _p(row_dev), table.shape[0], B, C, H * W,
-                                                 gen, float(grad_mul), _stream()), 'composite_mse_row')
-        return None, g, c
-    loss = torch.empty(B, device=a.device, dtype=torch.float32) if loss_out is None else loss_out
-    assert loss.shape == (B,) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == a.device
-    check(L.oodgan_composite_mse_fwd_bwd(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(loss), B, C, H * W, gen, float(grad_mul), _stream()),
-          'composite_mse')
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    if by_row:
+        check(L.oodgan_composite_mse_fwd_bwd_row(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), _p(row), nrows, B, C, H * W, gen,
+                                                 float(grad_mul), _stream()), 'composite_mse_row')
+    else:
+        check(L.oodgan_composite_mse_fwd_bwd(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), B, C, H * W, gen, float(grad_mul), _stream()),
+              'composite_mse')
     return loss, g, c
 
 
@@ -1289,14 +1295,12 @@ def ssim_loss_grad(img, target, gimg=None, grad_mul=1.0, loss_out=None, table=No
             'ssim_loss_grad: gimg must be a contiguous float32 tensor of the image\'s shape (it is updated in place)'
     L = _lib.lib()
     part = torch.empty(B, L.oodgan_ssim_nparts(C, H, W), device=a.device, dtype=torch.float32)
-    if table is not None:
-        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and row_dev.dtype == torch.int32
-        check(L.oodgan_ssim_loss_fwd_bwd_row(_p(a), _p(t), _p(gimg), _p(part), _p(table), _p(row_dev), table.shape[0], B, C, H, W, float(grad_mul),
-                                             _stream()), 'ssim_loss_row')
-        return None
-    loss = torch.empty(B, device=a.device, dtype=torch.float32) if loss_out is None else loss_out
-    assert loss.shape == (B,) and loss.dtype == torch.float32 and loss.is_contiguous() and loss.device == a.device
-    check(L.oodgan_ssim_loss_fwd_bwd(_p(a), _p(t), _p(gimg), _p(part), _p(loss), B, C, H, W, float(grad_mul), _stream()), 'ssim_loss')
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    if by_row:
+        check(L.oodgan_ssim_loss_fwd_bwd_row(_p(a), _p(t), _p(gimg), _p(part), _p(dst), _p(row), nrows, B, C, H, W, float(grad_mul), _stream()),
+              'ssim_loss_row')
+    else:
+        check(L.oodgan_ssim_loss_fwd_bwd(_p(a), _p(t), _p(gimg), _p(part), _p(dst), B, C, H, W, float(grad_mul), _stream()), 'ssim_loss')
     return loss
 
 

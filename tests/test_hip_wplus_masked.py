@@ -245,23 +245,38 @@ def test_blend_region_leaves_no_state_behind(dev):
 
 
 # ------------------------------------------------------------------------------------------------------- plans, streams
-def test_plans_and_streams_with_a_loss_weight(dev):
+@pytest.mark.parametrize('terms,steps', [((), 30), (('lpips',), 12), (('ssim',), 12), (('lpips', 'ssim'), 12)], ids=['none', 'lpips', 'ssim', 'lpips+ssim'])
+def test_plans_and_streams_with_a_loss_weight(dev, terms, steps):
+    """The recorded plan against the Python-driven loop, bit for bit, and two streams against one, for every set of terms taken on the composite
+    (LPIPS on seeded weights, as tests/test_hip_lpips.py).  The added term sets run 12 steps: nine replayed ones.  The two-stream bound is the one
+    of the plain masked loss for every set: the sub-batches differ from the batch in the kernels their sizes select, not in the loss."""
     from oodgan.engine import GeneratorEngine, WPlusInverter
-    size, B, steps = 256, 4, 30
+    from oodgan.lpips import LPIPSAlex
+    size, B = 256, 4
     eng = GeneratorEngine({k: v.to(dev) for k, v in synth.generator_state(size, seed=0).items()}, size)
     target = synth.make_images(size, B, seed=71).to(dev)
     noises = [n.to(dev) for n in synth.make_noises(size, B, seed=72)]
     w0 = synth.make_latents(size, B, seed=73, std=0.3).to(dev)
     beta = _beta(B, size, size, 74).to(dev)
-    inv = WPlusInverter(eng, use_plan=True)
+    kw = {}
+    if 'lpips' in terms:
+        kw.update(lpips=LPIPSAlex({k: v.to(dev) for k, v in synth.lpips_state(0).items()}, min_max=(-1.0, 1.0)), lpips_weight=0.8)
+    if 'ssim' in terms:
+        kw.update(ssim_weight=0.5)
+    inv = WPlusInverter(eng, use_plan=True, **kw)
     w1, l1 = inv.invert(target, w0, noises, steps=steps, loss_weight=beta)
+    t1 = {k: None if v is None else v.clone() for k, v in inv.last_terms.items()}
     assert inv.last_plan['steps'] == [steps - 3] and inv.last_stats['rollbacks'] == [0]
-    w2, l2 = WPlusInverter(eng, use_plan=False).invert(target, w0, noises, steps=steps, loss_weight=beta)
+    assert [k for k in ('lpips', 'ssim') if t1[k] is not None] == list(terms)
+    inv2 = WPlusInverter(eng, use_plan=False, **kw)
+    w2, l2 = inv2.invert(target, w0, noises, steps=steps, loss_weight=beta)
     assert torch.equal(w1, w2) and torch.equal(l1, l2)
+    assert inv2.last_plan['steps'] == [0] and all(torch.equal(t1[k], inv2.last_terms[k]) for k in ('mse',) + tuple(terms))
     w3, l3 = inv.invert(target, w0, noises, steps=steps, streams=2, loss_weight=beta)
     rel = ((l3 - l1).abs() / l1.abs()).max().item()
-    print(f'loss weight, 2 streams vs 1 at 256², B={B}: loss rel diff {rel:.2e}; plan {inv.last_plan}')
+    print(f'loss weight + {terms or "no term"}, 2 streams vs 1 at 256², B={B}: loss rel diff {rel:.2e}; plan {inv.last_plan}')
     assert rel < 5e-3 and inv.last_plan['steps'] == [steps - 3] * 2
+    assert all(inv.last_terms[k].shape == (steps, B) for k in ('mse',) + tuple(terms))
     assert (l1[-1] < l1[0]).all()
 
 

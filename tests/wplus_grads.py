@@ -1,8 +1,9 @@
 """TEST INFRASTRUCTURE — the W+ loop's per-step gradient, read back from the running inverter and checked in float64.
 
-``WPlusInverter`` never hands its gradient dL/dW+ to the caller: every step runs G(w), the MSE, the backward pass and Adam on the device
+``WPlusInverter`` never hands its gradient dL/dW+ to the caller: every step runs G(w), the loss (engine._WRun._loss_grad), the backward pass and Adam on the device
 (steps 4..N replayed from a launch plan).  What the caller can see after each step is (t, w, m) through ``inv.on_step``, and Adam's first
-moment is a lerp of the gradient (csrc/elementwise.hip, adam_kernel / adam_dev_kernel: ``m + (g - m) * (1 - beta1)`` in fp32), so
+moment is a lerp of the gradient (csrc/elementwise.hip, adam_dev_kernel — the loop's step index is a device counter in every mode:
+``m + (g - m) * (1 - beta1)`` in fp32), so
 
     g_t = m_{t-1} + (m_t - m_{t-1}) / (1 - beta1)
 
@@ -20,7 +21,7 @@ from oracle import ref_cpu as R
 
 
 class Capture:
-    """(w_t, m_t) of every (sub-)batch after every enqueued step, and w_0 / the cut points of the batch (engine._invert_runs)."""
+    """(w_t, m_t) of every (sub-)batch after every enqueued step, and w_0 / the cut points of the batch (engine.WPlusInverter._split)."""
 
     def __init__(self):
         self.steps = {}         # run index (= stream index) -> {t: (w, m)} on the run's device
@@ -71,7 +72,7 @@ def capture(inv):
         ns = max(1, min(int(streams), B))
         cap.steps.clear()
         cap.w0 = w0.detach().clone()
-        cap.cuts = [(i * B) // ns for i in range(ns + 1)]          # as engine.WPlusInverter._invert_runs splits the batch
+        cap.cuts = [(i * B) // ns for i in range(ns + 1)]          # as engine.WPlusInverter._split cuts the batch
         return invert(target, w0, noises, steps=steps, return_trajectory=return_trajectory, streams=streams, use_graph=use_graph)
 
     inv.on_step = on_step
