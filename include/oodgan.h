@@ -632,6 +632,28 @@ int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float
 /* same with the step index on the device: increments t_dev[0] first, then uses it (hipGraph-replayable W+ step) */
 int oodgan_adam_step_dev(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,
                          float beta2, float eps, int* t_dev, void* stream);
+/* Projector schedule of the W+ loop (csrc/wplus_sched.hip; anchors: rosinality stylegan2-pytorch projector.py, get_lr /
+ * latent_noise — the reference tree has no projector, the loop and its schedule are this build's).  Stateless: step counter, seed, ids and
+ * total_steps are arguments.
+ * oodgan_adam_step_dev with lr_i = lr * r(i), i = t_dev[0] - 1 after the increment (the zero-based step), tau = i / total_steps, in double:
+ * r = min(1, (1 - tau) / rampdown); r = 0.5 - 0.5 cos(pi r); r *= min(1, tau / rampup).  rampup <= 0 / rampdown <= 0: that factor is 1;
+ * both: bit-identical to oodgan_adam_step_dev.  r(0) = 0 with a ramp-up: the first step only fills the moments. */
+int oodgan_adam_step_dev_sched(float* w, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                               int* t_dev, int total_steps, float rampup, float rampdown, void* stream);
+/* w_in[b,e] = w[b,e] + sigma_i * n(seed, ids[b], i, e) for w, w_in (B, n_per_image); i = t_dev[0] (read, not incremented: the running
+ * step), sigma_i = sigma0 * max(0, 1 - (i / total_steps) / noise_ramp)^2 (noise_ramp <= 0: sigma0); sigma_i == 0: w_in = w bit for bit.
+ * n: Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) with key (seed lo, seed hi) and counter
+ * (e >> 2, id lo, i, id hi); outputs x0..x3 -> u_k = ((x_k >> 8) + 0.5) 2^-24; Box-Muller pairs (sqrt(-2 ln u0) cos 2 pi u1, ... sin 2 pi u1)
+ * and the same from (u2, u3); element e takes value e & 3.  ids: int64 (B) on the device.  A pure function of its arguments. */
+int oodgan_latent_noise(const float* w, float* w_in, const long* ids, const int* t_dev, int B, long n_per_image, long seed, int total_steps,
+                        float sigma0, float noise_ramp, void* stream);
+/* loss[b] = mean_e (w[b,e] - a[.,e])^2 and, with g != NULL, g[b,e] += weight * 2 (w - a) / n ACCUMULATED into g (the latent gradient the
+ * backward pass returned).  w, g (B, n); a (n) broadcast over the images (a_batched = 0) or (B, n).  One block per image, bit-reproducible. */
+int oodgan_latent_prior_fwd_bwd(const float* w, const float* a, float* g, float* loss, int B, long n, int a_batched, float weight,
+                                void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_latent_prior_fwd_bwd_row(const float* w, const float* a, float* g, float* loss_table, const int* row_dev, int nrows, int B,
+                                    long n, int a_batched, float weight, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

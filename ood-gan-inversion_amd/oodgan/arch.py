@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_ssim_weight
+from .engine import WPlusInverter, check_noise_seed, check_ssim_weight
 from .modules import Generator
 from .synth import generator_channels
 
@@ -262,7 +262,8 @@ class ood_faceGAN_e4e(nn.Module):
 
     # ---------------------------------------------------------------- build-defined: W+ refinement
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
-               ssim_weight=0.0, **kwargs):
+               ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
+               latent_anchor='start', **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -284,8 +285,20 @@ class ood_faceGAN_e4e(nn.Module):
         composite x + beta*(G(w) - x) with beta = (1 - alpha0)^blend_cnt, alpha0 the mask of the OOD forward at the start latents with the
         same ``noise`` — the error of the blended output this method returns, with the mask frozen for the run.  A float32 (B,1,S,S) tensor
         in [0,1] on the model's device: that beta (a caller mask: 0 = ignore the pixel).  ``self.last_loss_weight`` is the beta optimised
-        (None for 'full')."""
+        (None for 'full').
+        Projector schedule (rosinality's projector.py), all off by default.  ``lr_rampup`` / ``lr_rampdown`` (the projector's
+        0.05 / 0.25): fractions of the run over which the learning rate ramps up linearly and follows a cosine down.  ``latent_noise`` (its
+        ``--noise``, 0.05): Gaussian noise on the latent the generator reads, of strength latent_noise * ``generator.latent_std()`` *
+        max(0, 1 - (t / steps) / noise_ramp)^2; the draws depend on (``noise_seed``, the image's entry of ``noise_ids`` — int64 (B,), default
+        arange(B) —, step, element) only, not on the batch or the streams.  ``latent_reg`` > 0 adds latent_reg * mean (w - anchor)^2 per image
+        with ``latent_anchor`` = 'start' (the start latents of the run), 'mean' (avg_latent + delta_latent) or a (L,512) / (B,L,512) tensor;
+        ``last_loss_terms['latent']`` is its table (None when off).  Negative or non-finite values raise ValueError."""
         ssim_weight = check_ssim_weight(ssim_weight)
+        lr_rampup, lr_rampdown = check_ssim_weight(lr_rampup, 'lr_rampup'), check_ssim_weight(lr_rampdown, 'lr_rampdown')
+        latent_noise, noise_ramp = check_ssim_weight(latent_noise, 'latent_noise'), check_ssim_weight(noise_ramp, 'noise_ramp')
+        noise_seed, latent_reg = check_noise_seed(noise_seed), check_ssim_weight(latent_reg, 'latent_reg')
+        if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
+            raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
         if noise is None:
@@ -303,8 +316,17 @@ class ood_faceGAN_e4e(nn.Module):
                 st = lpips_state if lpips_state is not None else _seeded(0)
                 self._lpips_net, self._lpips_key = LPIPSAlex({k: v.to(x.device) for k, v in st.items()}, min_max=(-1.0, 1.0)), key
             lp = self._lpips_net
-        inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight)
-        w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta)
+        anchor = None
+        if latent_reg > 0.0:
+            anchor = latent_anchor
+            if not isinstance(anchor, torch.Tensor):
+                anchor = lats0 if anchor == 'start' else (self.avg_latent.reshape(1, -1, self.style_dim) + self.delta_latent)[0].expand(lats0.shape[1:])
+            anchor = anchor.detach().float().contiguous()
+        sigma0 = latent_noise * self.generator.latent_std() if latent_noise > 0.0 else 0.0
+        inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
+                            lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg)
+        w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
+                               latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise')}
         out, lats = self._ood_forward(x, w, enc_feats, noise=noise, **kw)

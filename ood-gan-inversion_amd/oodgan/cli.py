@@ -22,6 +22,15 @@ Where the W+ loss looks, in the same block:
     ssim_weight: <lambda>        adds lambda * (1 - SSIM) per image to the W+ loss: the SSIM this tool reports (11-tap Gaussian
                                  window, per channel), on the unrounded images, of the composite where a region is set.  Default 0 = off;
                                  negative or non-finite is an error.
+The projector schedule of the W+ loop (rosinality's projector.py), in the same block, everything off by default:
+
+    lr_rampup, lr_rampdown: <f>  fractions of the run over which the learning rate ramps up linearly / follows a cosine down (projector: 0.05, 0.25)
+    latent_noise: <f>            Gaussian noise on the latent the generator reads, in multiples of the generator's latent standard deviation
+                                 (projector: 0.05), decaying as max(0, 1 - (t / steps) / noise_ramp)^2; noise_ramp: <f> (default 0.75)
+    noise_seed: <int>            the seed of those draws (default 0); a file's draws depend on its index in the data set's sorted list, not on
+                                 ``batch`` or ``streams``
+    latent_reg: <lambda>         adds lambda * mean (w - anchor)^2 per image; latent_anchor: start | mean (the start latents of the run, default;
+                                 avg_latent + delta_latent)
 ``model_dict`` holds the reference's three variants (run_ood_faceGAN_inversion.py:23-27): the ``network_g`` blocks of
 options/test/{E4E,ReStyle,FeatureStyle}_Face_test.yml resolve unchanged.  LPIPS / identity need third-party weights that
 do not ship: they are reported as skipped."""
@@ -36,7 +45,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_ssim_weight
+from .engine import check_noise_seed, check_ssim_weight
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -111,6 +120,17 @@ def evaluate(gt_bgr, res_bgr, metrics, opt):
     return metrics
 
 
+def schedule_options(inv):
+    """The projector-schedule keywords of ``model.invert`` from the ``inversion`` block, checked (ValueError names the option)."""
+    defaults = dict(lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, latent_reg=0.0)
+    kw = {k: check_ssim_weight(inv.get(k, d), f'inversion.{k}') for k, d in defaults.items()}
+    kw['noise_seed'] = check_noise_seed(inv.get('noise_seed', 0), 'inversion.noise_seed')
+    kw['latent_anchor'] = inv.get('latent_anchor', 'start')
+    if kw['latent_anchor'] not in ('start', 'mean'):
+        raise ValueError(f"inversion.latent_anchor must be 'start' or 'mean', got {kw['latent_anchor']!r}")
+    return kw
+
+
 def run(opts, wplus_steps=None, log=None):
     log = log or logging.getLogger('oodgan.cli')
     inv = opts.get('inversion') or {}
@@ -120,6 +140,7 @@ def run(opts, wplus_steps=None, log=None):
     if mask_dir and loss_region != 'full':
         raise ValueError('inversion.mask_dir and inversion.loss_region: blend exclude each other')
     ssim_weight = check_ssim_weight(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
+    sched = schedule_options(inv)
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
     model = load_model(opts).cuda().eval()
@@ -156,7 +177,8 @@ def run(opts, wplus_steps=None, log=None):
                 t0 = time.time()
                 if steps > 0:
                     out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
-                                       loss_region=region, ssim_weight=ssim_weight)[0]
+                                       loss_region=region, ssim_weight=ssim_weight,
+                                       noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), **sched)[0]
                 else:
                     out = (graphed(x) if graphed is not None else model(x))[0]
                 torch.cuda.synchronize()

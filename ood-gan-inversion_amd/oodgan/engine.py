@@ -765,9 +765,13 @@ class _WRun:
     two flags are copied to pinned host memory on a side stream behind an event of the compute stream — no synchronisation of the compute
     stream; ``check_lag`` steps later (the copy has long finished: the host runs ahead of the GPU) the host looks at them.  Clear: the
     snapshot becomes the last clean state.  Set: the run goes back to the last clean state, repeats that window (<= check_every steps)
-    with exact scales, and continues in carry mode from freshly measured scales."""
+    with exact scales, and continues in carry mode from freshly measured scales.
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, beta=None):
+    Projector schedule: the learning-rate factor, the latent noise and its strength are functions of ``dev_t`` (and of the
+    run's constants: seed, image ids, ``steps``) evaluated inside the kernels — a rollback, which restores (w, m, v, t), needs nothing new: a
+    repeated window draws the same noise and takes the same learning rates."""
+
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, beta=None, ids=None, anchor=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -787,6 +791,13 @@ class _WRun:
         self.lp_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if self.lp is not None else None
         # optional SSIM term (csrc/loss_ssim.hip): a third loss table, 1 - SSIM per step and image
         self.ss_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.ssim_weight != 0.0 else None
+        # projector schedule (csrc/wplus_sched.hip).  ``w_in``, the perturbed latent the generator reads, is a persistent
+        # buffer like ``w``: born inside a recorded step it would be carved out of blocks the step's temporaries held (see ``use_plan`` below)
+        self.ids = ids
+        self.w_in = torch.empty_like(self.w) if inv.latent_noise != 0.0 else None
+        # latent prior: latent_reg * mean (w - anchor)^2 per image, a fourth loss table; the anchor is constant for the run
+        self.anchor = anchor
+        self.lat_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.latent_reg != 0.0 else None
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0
@@ -809,10 +820,18 @@ class _WRun:
     # ---- one W+ step on the current stream
     def _eager_step(self):
         eng, inv = self.eng, self.inv
-        img = eng.forward(self.w, self.noises, save=True, range_mode='carry')
+        w_in = self.w
+        if self.w_in is not None:
+            w_in = ops.latent_noise(self.w, self.dev_t, self.ids, self.steps, inv.latent_noise, inv.noise_ramp, inv.noise_seed, out=self.w_in)
+        img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
         gimg = self._loss_grad(img)
         g = eng.backward(gimg, self.gmul, carry_scale=True)
-        ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
+        if self.lat_table is not None:          # evaluated at w, not at the perturbed w_in
+            ops.latent_prior_loss_grad(self.w, self.anchor, g, inv.latent_reg, table=self.lat_table, row_dev=self.dev_t)
+        if inv.lr_rampup > 0.0 or inv.lr_rampdown > 0.0:
+            ops.adam_step_dev_sched(self.w, g, self.m, self.v, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown, inv.lr, inv.betas, inv.eps)
+        else:
+            ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
 
     def _loss_grad(self, img):
         """The loss of the step, each term's values to row dev_t of its table, and gmul * d(sum_b loss_b)/d(img).  The terms in the order
@@ -944,7 +963,7 @@ class _WRun:
 
 
 def check_ssim_weight(value, name='ssim_weight'):
-    """The weight of the SSIM loss term as a float; ValueError unless it is a finite number >= 0."""
+    """The weight of the SSIM loss term (or another option of that kind: ``name``) as a float; ValueError unless it is a finite number >= 0."""
     try:
         w = float(value)
     except (TypeError, ValueError):
@@ -952,6 +971,13 @@ def check_ssim_weight(value, name='ssim_weight'):
     if not (math.isfinite(w) and w >= 0.0):
         raise ValueError(f'{name} must be a finite number >= 0, got {value!r}')
     return w
+
+
+def check_noise_seed(value, name='noise_seed'):
+    """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
+    if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
+        raise ValueError(f'{name} must be an integer in [0, 2^63), got {value!r}')
+    return value
 
 
 class WPlusInverter:
@@ -963,19 +989,28 @@ class WPlusInverter:
     The loss of a step is defined once, in ``_WRun._loss_grad``: MSE (or the composite MSE with a loss weight) + lpips_weight * LPIPS +
     ssim_weight * (1 - SSIM); the step index is a device counter in every mode (plan, Python-driven, trajectory, any number of streams).
 
+    Projector schedule (rosinality's projector.py), every part off by default — the step is then the launch list above:
+    ``lr_rampup`` / ``lr_rampdown``: fractions of the run over which the learning rate ramps up linearly / follows a cosine down
+    (``ops.lr_multiplier``); ``latent_noise``: sigma_0, in latent units, of Gaussian noise added to the latent the generator reads, decaying as
+    max(0, 1 - (t / steps) / noise_ramp)^2 (``noise_ramp`` <= 0: constant), a function of (``noise_seed``, the image's id, step, element);
+    ``latent_reg``: adds latent_reg * mean (w - latent_anchor)^2 per image, evaluated at the unperturbed w (``last_terms['latent']``).
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}."""
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
-                 ssim_weight=0.0):
+                 ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
         # loss = per-image MSE + lpips_weight * LPIPS(alex) (north_star: "W+ Adam steps against LPIPS/L2"); ``lpips``: an oodgan.lpips.LPIPSAlex
         # (min_max = the generator's output range).  Off by default: the `lpips` weights are third-party and absent here (parity unpinned).
-        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'mse', 'lpips', 'ssim'} tables (None: term off).
+        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'mse', 'lpips', 'ssim', 'latent'} tables (None: term off).
         self.lpips, self.lpips_weight = lpips, float(lpips_weight)
         # + ssim_weight * (1 - SSIM) (DESIGN.md §15): the metric the CLI reports, on the unrounded images; 0 (default) = the term, its
         # kernel launches and its table do not exist
         self.ssim_weight = check_ssim_weight(ssim_weight)
+        self.lr_rampup, self.lr_rampdown = check_ssim_weight(lr_rampup, 'lr_rampup'), check_ssim_weight(lr_rampdown, 'lr_rampdown')
+        self.latent_noise, self.noise_ramp = check_ssim_weight(latent_noise, 'latent_noise'), check_ssim_weight(noise_ramp, 'noise_ramp')
+        self.noise_seed, self.latent_reg = check_noise_seed(noise_seed), check_ssim_weight(latent_reg, 'latent_reg')
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
@@ -989,13 +1024,18 @@ class WPlusInverter:
             self._pins.append(torch.zeros(2, dtype=torch.int32).pin_memory())
         return self._pins[i]
 
-    def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None):
+    def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None, noise_ids=None,
+               latent_anchor=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
         then share the GPU with the matrix kernels of the other instead of running back to back.
         ``loss_weight``: None (the per-image MSE) or a float32 (B,1,S,S) plane beta in [0,1] on the device — the loss is then taken on the
-        composite c = target + beta*(G(w) - target); a pixel with beta = 0 has no influence on the run."""
+        composite c = target + beta*(G(w) - target); a pixel with beta = 0 has no influence on the run.
+        ``noise_ids``: int64 (B,), the id each image draws its latent noise under (default arange(B)); it travels with the image into the
+        sub-batches, so an image sees the same noise on one stream or several and in any batch.  ``latent_anchor``: (L,512) or (B,L,512),
+        what ``latent_reg`` pulls towards (required when latent_reg > 0)."""
         B = w0.shape[0]
+        ids, anchor = self._sched_inputs(w0, noise_ids, latent_anchor)
         if loss_weight is not None:
             if tuple(loss_weight.shape) != (B, 1) + tuple(target.shape[2:]) or loss_weight.dtype != torch.float32 or loss_weight.device != target.device:
                 raise ValueError(f'loss_weight must be a float32 {(B, 1) + tuple(target.shape[2:])} tensor on {target.device}, got '
@@ -1015,7 +1055,7 @@ class WPlusInverter:
         if use_graph:
             return self._invert_graph(target, w0, noises, steps, streams)
         if streams == 1:
-            return self._invert_runs(target, w0, noises, steps, 1, return_trajectory, loss_weight)
+            return self._invert_runs(target, w0, noises, steps, 1, return_trajectory, loss_weight, ids, anchor)
         from . import _lib
         # the multi-stream threshold of the 8-wave stride-1 kernel, unless the caller set the tunable itself; the value that was read is
         # the one restored
@@ -1024,13 +1064,31 @@ class WPlusInverter:
         if override:
             _lib.set_tunable('s1_big_min_items', MULTI_STREAM_S1_BIG_MIN_ITEMS)
         try:
-            return self._invert_runs(target, w0, noises, steps, streams, False, loss_weight)
+            return self._invert_runs(target, w0, noises, steps, streams, False, loss_weight, ids, anchor)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', old)
 
-    def _split(self, target, w0, noises, beta, streams):
-        """(side streams, engines, [(target, w0, noises, beta)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams)."""
+    def _sched_inputs(self, w0, noise_ids, latent_anchor):
+        """(ids, anchor) of a call: the noise ids (None when the noise is off) and the prior's anchor (None when the prior is off), checked."""
+        B, ids, anchor = w0.shape[0], None, None
+        if self.latent_noise != 0.0:
+            ids = torch.arange(B, dtype=torch.int64, device=w0.device) if noise_ids is None else noise_ids
+            if not isinstance(ids, torch.Tensor) or tuple(ids.shape) != (B,) or ids.dtype != torch.int64 or ids.device != w0.device:
+                raise ValueError(f'noise_ids must be an int64 ({B},) tensor on {w0.device}')
+            ids = ids.contiguous()
+        if self.latent_reg != 0.0:
+            if latent_anchor is None:
+                raise ValueError('latent_reg > 0 needs latent_anchor: the latent the prior pulls towards')
+            anchor = latent_anchor
+            if (not isinstance(anchor, torch.Tensor) or tuple(anchor.shape) not in (tuple(w0.shape), tuple(w0.shape[1:]))
+                    or anchor.dtype != torch.float32 or anchor.device != w0.device):
+                raise ValueError(f'latent_anchor must be a float32 {tuple(w0.shape[1:])} or {tuple(w0.shape)} tensor on {w0.device}')
+            anchor = anchor.detach().contiguous()
+        return ids, anchor
+
+    def _split(self, target, w0, noises, beta, streams, ids=None, anchor=None):
+        """(side streams, engines, [(target, w0, noises, beta, ids, anchor)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams)."""
         B = w0.shape[0]
         cur = torch.cuda.current_stream()
         side = _side_streams(w0.device, streams)
@@ -1045,7 +1103,9 @@ class WPlusInverter:
         for i in range(streams):
             sl = slice((i * B) // streams, ((i + 1) * B) // streams)
             parts.append((target[sl].contiguous(), w0[sl].detach().contiguous(),
-                          [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous()))
+                          [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous(),
+                          None if ids is None else ids[sl].contiguous(),
+                          anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor))
         for st in side:
             st.wait_stream(cur)                 # AFTER the slices above were enqueued on the caller's stream
         return side, engines, parts
@@ -1064,19 +1124,19 @@ class WPlusInverter:
                     t.record_stream(cur)
         return out
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, beta=None):
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, beta=None, ids=None, anchor=None):
         self._runs = []
         if streams == 1:
             eng = self.engine
             eng.reset_bwd_state()
             eng.reset_fwd_state()
-            runs = [_WRun(self, eng, target, w0, noises, steps, None, return_trajectory, beta)]
+            runs = [_WRun(self, eng, target, w0, noises, steps, None, return_trajectory, beta, ids, anchor)]
         else:
-            side, engines, parts = self._split(target, w0, noises, beta, streams)
+            side, engines, parts = self._split(target, w0, noises, beta, streams, ids, anchor)
             runs = []
             for i, st in enumerate(side):
                 with torch.cuda.stream(st):         # state tensors initialised on the stream that uses them
-                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, False, parts[i][3]))
+                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, False, *parts[i][3:]))
         try:
             busy = True
             while busy:
@@ -1090,15 +1150,17 @@ class WPlusInverter:
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         if streams == 1:
             r = runs[0]
-            losses = self._total(r.lbuf, r.lp_table, r.ss_table)
+            losses = self._total(r.lbuf, r.lp_table, r.ss_table, r.lat_table)
             return (r.w, losses, r.traj) if return_trajectory else (r.w, losses)
-        w, mse, lp, ss = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs]])
-        return w, self._total(mse, lp, ss)
+        w, mse, lp, ss, lat = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
+                                                                       [r.lat_table for r in runs]])
+        return w, self._total(mse, lp, ss, lat)
 
-    def _total(self, mse, lp, ss=None):
-        self.last_terms = {'mse': mse, 'lpips': lp, 'ssim': ss}
+    def _total(self, mse, lp, ss=None, lat=None):
+        self.last_terms = {'mse': mse, 'lpips': lp, 'ssim': ss, 'latent': lat}
         total = mse if lp is None else mse + self.lpips_weight * lp
-        return total if ss is None else total + self.ssim_weight * ss
+        total = total if ss is None else total + self.ssim_weight * ss
+        return total if lat is None else total + self.latent_reg * lat
 
     def _invert_graph(self, target, w0, noises, steps, streams):
         """hipGraph replay of one captured W+ step per stream (measured 3 % slower than eager launches on this host; kept as an
@@ -1108,6 +1170,8 @@ class WPlusInverter:
             raise NotImplementedError('use_graph with the LPIPS term: use the launch plans (default) instead')
         if self.ssim_weight != 0.0:
             raise NotImplementedError('use_graph with the SSIM term: use the launch plans (default) instead')
+        if self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0:
+            raise NotImplementedError('use_graph with the projector schedule (lr ramps, latent noise, latent prior): use the launch plans (default) instead')
         side, engines, split = self._split(target, w0, noises, None, streams)
         gmul = ops.loss_scale_for(target.numel() // w0.shape[0])
         dev = w0.device

@@ -281,6 +281,20 @@ class Generator(nn.Module):
     def get_latent(self, input):
         return self.style(input)
 
+    @torch.no_grad()
+    def latent_std(self, n=10000, seed=0):
+        """The scalar spread of W that rosinality's projector.py scales its latent noise by: sqrt(sum (w - mean w)^2 / n) over the mapping
+        network's outputs for ``n`` samples z ~ N(0, I) — drawn on the CPU from ``seed``, so the value does not depend on the device's
+        generator.  Cached per (n, seed) for the mapping weights in use."""
+        key = (int(n), int(seed), tuple((t.data_ptr(), t._version) for t in self.style.parameters()))
+        cache = self.__dict__.setdefault('_latent_std', {})
+        if key not in cache:
+            z = torch.randn(int(n), self.style_dim, generator=torch.Generator().manual_seed(int(seed)))
+            w = self.style(z.to(self.input.input.device))
+            cache.clear()                   # other weights: the old entries can never be hit again
+            cache[key] = float(((w - w.mean(0, keepdim=True)).double().pow(2).sum() / int(n)).sqrt().item())
+        return cache[key]
+
     def _draw_noises(self, batch, noise, randomize_noise):
         if noise is None:
             if randomize_noise:
@@ -459,6 +473,9 @@ class StyleGAN2Generator(nn.Module):
 
     def mean_latent(self, num_latent):
         return self._inner[0].mean_latent(num_latent)
+
+    def latent_std(self, n=10000, seed=0):
+        return self._inner[0].latent_std(n, seed)
 
     def forward(self, styles, input_is_latent=False, input_is_tensor=False, noise=None, randomize_noise=True, truncation=1,
                 truncation_latent=None, inject_index=None, return_latents=False, conditions=None, cond_layers=None,

@@ -1365,3 +1365,68 @@ def adam_step_dev(w, g, m, v, t_dev, lr=0.01, betas=(0.9, 0.999), eps=1e-8):
     check(_lib.lib().oodgan_adam_step_dev(_p(w), _p(_dev(g)), _p(m), _p(v), w.numel(), float(lr), float(betas[0]),
                                           float(betas[1]), float(eps), _p(t_dev), _stream()), 'adam_dev')
     return w
+
+
+# ---- projector schedule of the W+ loop (csrc/wplus_sched.hip)
+def lr_multiplier(i, total_steps, rampup, rampdown):
+    """The learning-rate factor of zero-based step ``i`` of ``total_steps`` (rosinality's projector.py ``get_lr`` without its initial lr; the
+    host restatement of what oodgan_adam_step_dev_sched derives from the device counter): min(1, (1 - tau) / rampdown) through
+    0.5 - 0.5 cos(pi r), times min(1, tau / rampup), tau = i / total_steps.  A ramp <= 0 switches its factor off."""
+    tau = i / total_steps
+    r = 1.0
+    if rampdown > 0:
+        r = min(1.0, (1.0 - tau) / rampdown)
+        r = 0.5 - 0.5 * math.cos(math.pi * r)
+    if rampup > 0:
+        r *= min(1.0, tau / rampup)
+    return r
+
+
+def adam_step_dev_sched(w, g, m, v, t_dev, total_steps, rampup, rampdown, lr=0.01, betas=(0.9, 0.999), eps=1e-8):
+    """``adam_step_dev`` with lr * lr_multiplier(t_dev[0], total_steps, rampup, rampdown) taken on the device (t_dev is incremented first, as
+    there); both ramps <= 0: the same bits as ``adam_step_dev``."""
+    check(_lib.lib().oodgan_adam_step_dev_sched(_p(w), _p(_dev(g)), _p(m), _p(v), w.numel(), float(lr), float(betas[0]), float(betas[1]),
+                                                float(eps), _p(t_dev), int(total_steps), float(rampup), float(rampdown), _stream()),
+          'adam_dev_sched')
+    return w
+
+
+def latent_noise(w, t_dev, ids, total_steps, sigma0, noise_ramp=0.75, seed=0, out=None):
+    """w_in = w + sigma_i * n(seed, ids[b], i, e) (oodgan_latent_noise): w (B, ...) float32, i = t_dev[0] (int32[1] on the device, not
+    changed), ids int64 (B,) on the device, sigma_i = sigma0 * max(0, 1 - (i / total_steps) / noise_ramp)^2 (noise_ramp <= 0: sigma0).  The
+    draws are a pure function of (seed, id, step, element) — tests/latent_noise_ref.py restates them in float64.  ``out``: the buffer
+    that receives w_in (the W+ loop's persistent one); returns it."""
+    a = _dev(w, 'w')
+    B = a.shape[0]
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.shape == a.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == a.device
+    assert ids.shape == (B,) and ids.dtype == torch.int64 and ids.is_contiguous() and ids.device == a.device, \
+        'latent_noise: ids must be a contiguous int64 (B,) tensor on the latent\'s device'
+    assert t_dev.dtype == torch.int32 and t_dev.device == a.device
+    check(_lib.lib().oodgan_latent_noise(_p(a), _p(out), _p(ids), _p(t_dev), B, a.numel() // B, int(seed), int(total_steps), float(sigma0),
+                                         float(noise_ramp), _stream()), 'latent_noise')
+    return out
+
+
+def latent_prior_loss_grad(w, anchor, g=None, weight=1.0, loss_out=None, table=None, row_dev=None):
+    """The latent prior (oodgan_latent_prior_fwd_bwd): per image mean_e (w - anchor)^2 for w (B, ...) and ``anchor`` of one image's shape
+    (broadcast over the batch) or of w's.  ``g`` (w's shape, contiguous): g += weight * 2 (w - anchor) / n, accumulated into the latent
+    gradient ``backward`` returned; None: forward only.  Returns the (B,) values, or None with ``table``; ``loss_out`` / ``table`` +
+    ``row_dev``: as ``mse_loss_grad``."""
+    a, c = _dev(w, 'w'), _dev(anchor, 'anchor')
+    B = a.shape[0]
+    if tuple(c.shape) not in (tuple(a.shape), tuple(a.shape[1:])):
+        raise ValueError(f'latent_prior_loss_grad: anchor must have shape {tuple(a.shape[1:])} or {tuple(a.shape)}, got {tuple(c.shape)}')
+    if g is not None:
+        assert g.shape == a.shape and g.dtype == torch.float32 and g.is_contiguous() and g.device == a.device, \
+            'latent_prior_loss_grad: g must be a contiguous float32 tensor of the latent\'s shape (it is updated in place)'
+    n, batched = a.numel() // B, int(c.dim() == a.dim())
+    L = _lib.lib()
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    if by_row:
+        check(L.oodgan_latent_prior_fwd_bwd_row(_p(a), _p(c), _p(g), _p(dst), _p(row), nrows, B, n, batched, float(weight), _stream()),
+              'latent_prior_row')
+    else:
+        check(L.oodgan_latent_prior_fwd_bwd(_p(a), _p(c), _p(g), _p(dst), B, n, batched, float(weight), _stream()), 'latent_prior')
+    return loss
