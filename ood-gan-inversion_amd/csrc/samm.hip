@@ -19,6 +19,14 @@ __device__ __forceinline__ float sqacc(float q, float x, float mean) {
     return __fadd_rn(q, __fmul_rn(a, a));
 }
 
+// a + b with b rounded on its own.  The fused passes below add values they have just computed AND stored: their statistics are those of the
+// stored tensor (bit-identical to instnorm_stats_kernel on it) only if the product that made b is not contracted into this sum —
+// __fmul_rn is a plain product to the compiler, and `sb += e_` became a v_fmac wherever a thread made more than one scalar trip
+__device__ __forceinline__ float add_rounded(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+
 // ---------------------------------------------------------------- InstanceNorm statistics
 // one block per (b,c) plane; two passes (mean, then centred second moment) — the plane (<=256 KB)
 // is served from L2 on the second pass.
@@ -228,7 +236,8 @@ __global__ __launch_bounds__(256) void align_input_stats_kernel(const float* __r
                     reinterpret_cast<float4*>(o0)[i + 256 * u] = d_;
                     reinterpret_cast<float4*>(o1)[i + 256 * u] = e_;
                 }
-                const float ta = live ? (d_.x + d_.y) + (d_.z + d_.w) : 0.f, tb = live ? (e_.x + e_.y) + (e_.z + e_.w) : 0.f;
+                const float ta = live ? add_rounded(add_rounded(d_.x, d_.y), add_rounded(d_.z, d_.w)) : 0.f;
+                const float tb = live ? add_rounded(add_rounded(e_.x, e_.y), add_rounded(e_.z, e_.w)) : 0.f;
                 if (u == 0) { a0 += ta; b0 += tb; } else if (u == 1) { a1 += ta; b1 += tb; } else if (u == 2) { a2 += ta; b2 += tb; } else { a3 += ta; b3 += tb; }
             }
         }
@@ -238,7 +247,7 @@ __global__ __launch_bounds__(256) void align_input_stats_kernel(const float* __r
         for (long i = threadIdx.x; i < HW; i += 256) {
             const float e_ = align_e(ep[i], me, re), d_ = align_d(gp[i], mg, rg, diff ? e_ : 0.f);
             o0[i] = d_; o1[i] = e_;
-            sa += d_; sb += e_;
+            sa = add_rounded(sa, d_); sb = add_rounded(sb, e_);
         }
     }
     sa = block_sum_256(sa, red);
@@ -727,7 +736,9 @@ __global__ __launch_bounds__(256) void align_head_kernel(const float* __restrict
     for (long e = blockIdx.x * 256L + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const int c = (int)((e / HW) % 3);
         const float v = x[e];
-        y[e] = c < 2 ? tanhf(v) * scale : 1.f / (1.f + expf(-v));
+        // below -87, 1 + expf(v) rounds to 1 and the sigmoid is expf(v) itself (down to the denormals); expf(-v) overflows from 88.72 on,
+        // where the quotient returned 0 for 2.7e-39
+        y[e] = c < 2 ? tanhf(v) * scale : (v < -87.f ? expf(v) : 1.f / (1.f + expf(-v)));
     }
 }
 
