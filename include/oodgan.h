@@ -60,7 +60,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]) and "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]) and "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);
@@ -625,6 +625,26 @@ int oodgan_ssim_loss_fwd_bwd(const float* img, const float* target, float* gimg,
 int oodgan_ssim_loss_fwd_bwd_row(const float* img, const float* target, float* gimg, float* part, float* loss_table, const int* row_dev,
                                  int nrows, int B, int C, int H, int W, float grad_mul, void* stream);
 int oodgan_ssim_nparts(int C, int H, int W);
+/* Robust pixel terms of the W+ loss: loss[b] = mean_{c,p} rho(d) in place of the MSE, d = img - target (beta NULL) or
+ * d = beta*(img - target) on the composite c = target + d of oodgan_composite_mse_fwd_bwd (beta (B,1,HW)); s = scale, s2 = s*s in float32:
+ *   OODGAN_ROBUST_CHARBONNIER    rho = sqrt(d^2 + s2)                         psi = rho' = d / sqrt(d^2 + s2)
+ *   OODGAN_ROBUST_HUBER          rho = d^2/2 if |d| <= s, else s(|d| - s/2)   psi = clamp(d, -s, s)
+ *   OODGAN_ROBUST_GEMAN_MCCLURE  rho = d^2 r / 2, r = s2 / (d^2 + s2)         psi = d r^2 (an outlier's pull goes to zero)
+ * anchors: charbonnier_loss with eps = s2 (BasicSR/basicsr/losses/losses.py:25-26); torch.nn.functional.huber_loss(delta = s); the
+ * reference has no Geman-McClure term.  Huber with s above every |d| is half the MSE.
+ * gimg (B,C,HW) or NULL (forward only, the same loss bit for bit) = grad_mul/(C*HW) * psi(d), the gradient w.r.t. c, or with beta and
+ * wrt_gen = 1 that times beta (w.r.t. img); comp (B,C,HW) or NULL receives c (needs beta).  A beta = 0 pixel adds the constant rho(0)
+ * (s for Charbonnier, else 0) and no gradient; beta == 1 gives the plain form's loss and gimg bit for bit.  part: (B,
+ * oodgan_mse_nparts(C*HW)) scratch; two-stage sums, no float atomics: bit-reproducible.  OODGAN_E_ARG with a message for an unknown
+ * kind and for a scale that is not finite and > 0 with a normal float32 square (about 1.1e-19 < s < 1.8e19).  Counted by the dispatch
+ * counter "robust". */
+enum { OODGAN_ROBUST_CHARBONNIER = 1, OODGAN_ROBUST_HUBER = 2, OODGAN_ROBUST_GEMAN_MCCLURE = 3 };
+int oodgan_robust_loss_fwd_bwd(const float* img, const float* target, const float* beta, float* gimg, float* comp, float* part,
+                               float* loss, int B, int C, long HW, int kind, float scale, int wrt_gen, float grad_mul, void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_robust_loss_fwd_bwd_row(const float* img, const float* target, const float* beta, float* gimg, float* comp, float* part,
+                                   float* loss_table, const int* row_dev, int nrows, int B, int C, long HW, int kind, float scale,
+                                   int wrt_gen, float grad_mul, void* stream);
 /* torch.optim.Adam step (no weight decay, no amsgrad), step index t>=1 given by the host:
  * anchors: get_optimizer (src/models/OOD_faceGAN_model.py:398-400). */
 int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,

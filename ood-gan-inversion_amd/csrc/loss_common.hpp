@@ -1,11 +1,11 @@
-// What the loss terms of the W+ step share (elementwise.hip: MSE; loss_masked.hip: composite MSE; loss_ssim.hip; lpips.hip): every term
+// What the loss terms of the W+ step share (elementwise.hip: MSE; loss_masked.hip: composite MSE; loss_robust.hip: robust rho; loss_ssim.hip; lpips.hip): every term
 // reduces per-block partial sums to one value per image and writes it either to loss[b] or to a row of the loop's (nrows, B) loss table.
 #pragma once
 #include "common.hpp"
 
 namespace oodgan {
 
-// elements per block of mse_kernel and of the composite kernels = elements per partial sum (oodgan_mse_nparts)
+// elements per block of mse_kernel, of the composite and of the robust kernels = elements per partial sum (oodgan_mse_nparts)
 constexpr int kMseChunk = 16384;
 
 // Offset of the row the losses of B images go to.  row_dev != NULL: row min(row_dev[0], nrows - 1) of a (nrows, B) table — the W+ loop's

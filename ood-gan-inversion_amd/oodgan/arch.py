@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_noise_seed, check_ssim_weight
+from .engine import WPlusInverter, check_noise_seed, check_pixel_loss, check_ssim_weight
 from .modules import Generator
 from .synth import generator_channels
 
@@ -263,7 +263,7 @@ class ood_faceGAN_e4e(nn.Module):
     # ---------------------------------------------------------------- build-defined: W+ refinement
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
-               latent_anchor='start', **kwargs):
+               latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -292,11 +292,19 @@ class ood_faceGAN_e4e(nn.Module):
         max(0, 1 - (t / steps) / noise_ramp)^2; the draws depend on (``noise_seed``, the image's entry of ``noise_ids`` — int64 (B,), default
         arange(B) —, step, element) only, not on the batch or the streams.  ``latent_reg`` > 0 adds latent_reg * mean (w - anchor)^2 per image
         with ``latent_anchor`` = 'start' (the start latents of the run), 'mean' (avg_latent + delta_latent) or a (L,512) / (B,L,512) tensor;
-        ``last_loss_terms['latent']`` is its table (None when off).  Negative or non-finite values raise ValueError."""
+        ``last_loss_terms['latent']`` is its table (None when off).  Negative or non-finite values raise ValueError.
+        ``pixel_loss``: the pixel term, the per-image mean of rho(d) over the residual d = G - x (beta*(G - x) where ``loss_region``
+        selects a composite).  'mse' (default): d^2, the path above unchanged.  Robust kinds, for occluders nobody masked, with the scale
+        s = ``pixel_scale`` in image units: 'charbonnier' sqrt(d^2 + s^2) (BasicSR's CharbonnierLoss with eps = s^2), 'huber' d^2/2 up to
+        |d| = s and s(|d| - s/2) beyond (a very large s is half the MSE), 'geman_mcclure' d^2/2 * s^2/(d^2 + s^2), whose pull on the latent
+        goes to zero for an outlier.  The default s = 0.1 is a tenth of the image half-range, about 13 grey levels: a choice, not a measured
+        optimum.  ``last_loss_terms['pixel']`` is the term's table whatever its kind; ``['mse']`` is that table for 'mse' and None otherwise.
+        An unknown name, or a scale that is not a finite number > 0, raises ValueError; ``use_graph`` with a robust kind NotImplementedError."""
         ssim_weight = check_ssim_weight(ssim_weight)
         lr_rampup, lr_rampdown = check_ssim_weight(lr_rampup, 'lr_rampup'), check_ssim_weight(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_ssim_weight(latent_noise, 'latent_noise'), check_ssim_weight(noise_ramp, 'noise_ramp')
         noise_seed, latent_reg = check_noise_seed(noise_seed), check_ssim_weight(latent_reg, 'latent_reg')
+        pixel_loss, pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         lats0, enc_feats = self.encode(x, **kwargs)
@@ -324,7 +332,8 @@ class ood_faceGAN_e4e(nn.Module):
             anchor = anchor.detach().float().contiguous()
         sigma0 = latent_noise * self.generator.latent_std() if latent_noise > 0.0 else 0.0
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
-                            lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg)
+                            lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
+                            pixel_loss=pixel_loss, pixel_scale=pixel_scale)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
                                latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan

@@ -22,6 +22,11 @@ Where the W+ loss looks, in the same block:
     ssim_weight: <lambda>        adds lambda * (1 - SSIM) per image to the W+ loss: the SSIM this tool reports (11-tap Gaussian
                                  window, per channel), on the unrounded images, of the composite where a region is set.  Default 0 = off;
                                  negative or non-finite is an error.
+    pixel_loss: mse | charbonnier | huber | geman_mcclure
+                                 the pixel term: the mean of d^2 (default), sqrt(d^2 + s^2), Huber's d^2/2 up to |d| = s and
+                                 s(|d| - s/2) beyond, or d^2/2 * s^2/(d^2 + s^2) over the residual d — robust kinds for occluders nobody masked.
+    pixel_scale: <s>             their scale in image units ([-1,1] images), a finite number > 0.  Default 0.1, a tenth of the half-range (about
+                                 13 grey levels): a choice, not a measured optimum.  huber with a very large s is half the MSE.
 The projector schedule of the W+ loop (rosinality's projector.py), in the same block, everything off by default:
 
     lr_rampup, lr_rampdown: <f>  fractions of the run over which the learning rate ramps up linearly / follows a cosine down (projector: 0.05, 0.25)
@@ -45,7 +50,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_noise_seed, check_ssim_weight
+from .engine import check_noise_seed, check_pixel_loss, check_ssim_weight
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -140,6 +145,8 @@ def run(opts, wplus_steps=None, log=None):
     if mask_dir and loss_region != 'full':
         raise ValueError('inversion.mask_dir and inversion.loss_region: blend exclude each other')
     ssim_weight = check_ssim_weight(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
+    pixel_loss, pixel_scale = check_pixel_loss(inv.get('pixel_loss', 'mse'), inv.get('pixel_scale', 0.1), 'inversion.pixel_loss',
+                                               'inversion.pixel_scale')
     sched = schedule_options(inv)
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
@@ -177,7 +184,7 @@ def run(opts, wplus_steps=None, log=None):
                 t0 = time.time()
                 if steps > 0:
                     out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
-                                       loss_region=region, ssim_weight=ssim_weight,
+                                       loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale,
                                        noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), **sched)[0]
                 else:
                     out = (graphed(x) if graphed is not None else model(x))[0]

@@ -9,6 +9,7 @@ latents, and the W+ Adam inversion loop.
     of a whole forward is one MFMA contraction and its backward one kernel.
 Layer order / latent indexing follow reference src/ops/StyleGAN/model.py:548-576."""
 import math
+import numbers
 import re
 
 import os
@@ -835,12 +836,16 @@ class _WRun:
 
     def _loss_grad(self, img):
         """The loss of the step, each term's values to row dev_t of its table, and gmul * d(sum_b loss_b)/d(img).  The terms in the order
-        they accumulate into the gradient: the MSE writes it, LPIPS and 1 - SSIM add lambda * gmul * their part.  With a loss weight beta
+        they accumulate into the gradient: the pixel term (the MSE, or the robust term ``pixel_loss`` names) writes it, LPIPS and 1 - SSIM add
+        lambda * gmul * their part.  With a loss weight beta
         the terms are taken on the composite c: alone, the composite MSE writes beta*dL/dc in one kernel; with LPIPS or
         SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
         on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
-        if self.beta is None:
+        if inv.pixel_loss != 'mse':             # a robust rho(d) in the MSE's place, same flags (csrc/loss_robust.hip)
+            _, gimg, c = ops.robust_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if on_c else 'gen',
+                                              composite=on_c, table=self.lbuf, row_dev=row)
+        elif self.beta is None:
             _, gimg = ops.mse_loss_grad(img, self.target, gmul, table=self.lbuf, row_dev=row)
         else:
             _, gimg, c = ops.composite_mse_loss_grad(img, self.target, self.beta, gmul, wrt='composite' if on_c else 'gen', composite=on_c,
@@ -973,6 +978,24 @@ def check_ssim_weight(value, name='ssim_weight'):
     return w
 
 
+PIXEL_LOSSES = ('mse',) + tuple(ops.ROBUST_KINDS)
+
+
+def check_pixel_loss(pixel_loss, pixel_scale, name='pixel_loss', scale_name='pixel_scale'):
+    """The pixel term of the W+ loss and its scale as (name, s): ValueError unless the name is one of PIXEL_LOSSES and the scale a finite real
+    number > 0 (not a string, not a bool).  s is the scale rounded to float32, the value the kernel uses; its float32 square must be a normal
+    number (about 1.1e-19 < s < 1.8e19), or d^2 + s^2 could be 0 or inf."""
+    if not isinstance(pixel_loss, str) or pixel_loss not in PIXEL_LOSSES:
+        raise ValueError(f'{name} must be one of {list(PIXEL_LOSSES)}, got {pixel_loss!r}')
+    if isinstance(pixel_scale, bool) or not isinstance(pixel_scale, numbers.Real) or not (math.isfinite(pixel_scale) and pixel_scale > 0):
+        raise ValueError(f'{scale_name} must be a finite number > 0, got {pixel_scale!r}')
+    s = torch.tensor(float(pixel_scale), dtype=torch.float32)
+    s2 = (s * s).item()
+    if not (math.isfinite(s2) and s2 >= torch.finfo(torch.float32).tiny):
+        raise ValueError(f'{scale_name} must have a normal float32 square (about 1.1e-19 < s < 1.8e19), got {pixel_scale!r}')
+    return pixel_loss, s.item()
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -986,7 +1009,7 @@ class WPlusInverter:
     ``noise=<list>`` (model.py:483-585), torch.optim.Adam as built by get_optimizer
     (src/models/OOD_faceGAN_model.py:398-400), basicsr MSELoss (losses.py:58-83).
 
-    The loss of a step is defined once, in ``_WRun._loss_grad``: MSE (or the composite MSE with a loss weight) + lpips_weight * LPIPS +
+    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight) — + lpips_weight * LPIPS +
     ssim_weight * (1 - SSIM); the step index is a device counter in every mode (plan, Python-driven, trajectory, any number of streams).
 
     Projector schedule (rosinality's projector.py), every part off by default — the step is then the launch list above:
@@ -999,11 +1022,17 @@ class WPlusInverter:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}."""
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
-                 ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0):
+                 ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
+                 pixel_loss='mse', pixel_scale=0.1):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # the pixel term: 'mse' (default: today's kernels and launch list) or a robust rho of the residual with scale ``pixel_scale`` in image
+        # units — 'charbonnier', 'huber' (a very large scale: half the MSE), 'geman_mcclure' (DESIGN.md §5).  The default scale 0.1, a tenth of
+        # the image half-range (about 13 grey levels), is a choice, not a measured optimum
+        self.pixel_loss, self.pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
         # loss = per-image MSE + lpips_weight * LPIPS(alex) (north_star: "W+ Adam steps against LPIPS/L2"); ``lpips``: an oodgan.lpips.LPIPSAlex
         # (min_max = the generator's output range).  Off by default: the `lpips` weights are third-party and absent here (parity unpinned).
-        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'mse', 'lpips', 'ssim', 'latent'} tables (None: term off).
+        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'pixel', 'mse', 'lpips', 'ssim', 'latent'} tables (None: term off;
+        # 'pixel' is the pixel term's table whatever its kind, 'mse' the same tensor when ``pixel_loss`` is 'mse' and None otherwise).
         self.lpips, self.lpips_weight = lpips, float(lpips_weight)
         # + ssim_weight * (1 - SSIM) (DESIGN.md §15): the metric the CLI reports, on the unrounded images; 0 (default) = the term, its
         # kernel launches and its table do not exist
@@ -1157,7 +1186,7 @@ class WPlusInverter:
         return w, self._total(mse, lp, ss, lat)
 
     def _total(self, mse, lp, ss=None, lat=None):
-        self.last_terms = {'mse': mse, 'lpips': lp, 'ssim': ss, 'latent': lat}
+        self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         return total if lat is None else total + self.latent_reg * lat
@@ -1170,6 +1199,8 @@ class WPlusInverter:
             raise NotImplementedError('use_graph with the LPIPS term: use the launch plans (default) instead')
         if self.ssim_weight != 0.0:
             raise NotImplementedError('use_graph with the SSIM term: use the launch plans (default) instead')
+        if self.pixel_loss != 'mse':
+            raise NotImplementedError('use_graph with a robust pixel term: use the launch plans (default) instead')
         if self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0:
             raise NotImplementedError('use_graph with the projector schedule (lr ramps, latent noise, latent prior): use the launch plans (default) instead')
         side, engines, split = self._split(target, w0, noises, None, streams)

@@ -1272,6 +1272,45 @@ def composite_mse_loss_grad(img, target, beta, grad_mul=1.0, wrt='gen', composit
     return loss, g, c
 
 
+# kinds of the robust pixel term (include/oodgan.h, OODGAN_ROBUST_*)
+ROBUST_KINDS = {'charbonnier': 1, 'huber': 2, 'geman_mcclure': 3}
+
+
+def robust_loss_grad(img, target, kind, scale, beta=None, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None, row_dev=None,
+                     grad=True):
+    """A robust pixel term in place of the MSE (oodgan_robust_loss_fwd_bwd): per-image mean of rho(d), d = img - target or, with a
+    loss weight ``beta`` (B,1,H,W), d = beta*(img - target) on the composite c = target + d.  ``kind``: 'charbonnier' sqrt(d^2 + s^2), 'huber'
+    (d^2/2 up to |d| = s, then s(|d| - s/2); a very large s gives half the MSE) or 'geman_mcclure' (d^2/2 * s^2/(d^2 + s^2)); ``scale``: s > 0, used
+    as a float32.  The gradient is grad_mul/CHW * rho'(d), w.r.t. the composite (``wrt='composite'``) or times beta once more (``wrt='gen'``);
+    ``composite=True`` (needs beta) also returns c; ``grad=False``: forward only, the same loss bit for bit.  Returns (loss[B] or None with
+    ``table``, gimg or None, c or None); ``loss_out`` / ``table`` + ``row_dev``: as ``mse_loss_grad``.  beta == 1 gives the plain form's loss and
+    gradient bit for bit."""
+    a, t = _dev(img, 'img'), _dev(target, 'target')
+    if a.dim() != 4 or a.shape != t.shape:
+        raise ValueError(f'robust_loss_grad: img and target must be (B,C,H,W) of one shape, got {tuple(a.shape)} and {tuple(t.shape)}')
+    if kind not in ROBUST_KINDS:
+        raise ValueError(f'kind must be one of {sorted(ROBUST_KINDS)}, got {kind!r}')
+    if wrt not in ('gen', 'composite'):
+        raise ValueError(f"wrt must be 'gen' or 'composite', got {wrt!r}")
+    w = None if beta is None else _plane(beta, a)
+    if composite and w is None:
+        raise ValueError('composite=True needs beta: without a loss weight the composite is the image')
+    B, C, H, W = a.shape
+    L = _lib.lib()
+    part = torch.empty(B, L.oodgan_mse_nparts(C * H * W), device=a.device, dtype=torch.float32)
+    g = torch.empty_like(a) if grad else None
+    c = torch.empty_like(a) if composite else None
+    k, gen = ROBUST_KINDS[kind], 1 if wrt == 'gen' else 0
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    if by_row:
+        check(L.oodgan_robust_loss_fwd_bwd_row(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), _p(row), nrows, B, C, H * W, k, float(scale),
+                                               gen, float(grad_mul), _stream()), 'robust_loss_row')
+    else:
+        check(L.oodgan_robust_loss_fwd_bwd(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), B, C, H * W, k, float(scale), gen,
+                                           float(grad_mul), _stream()), 'robust_loss')
+    return loss, g, c
+
+
 def scale_by_plane(g, beta):
     """g (B,C,H,W) <- beta (B,1,H,W) * g in place (oodgan_scale_by_plane); returns g."""
     assert g.is_contiguous(), 'scale_by_plane: g must be contiguous (it is updated in place)'
