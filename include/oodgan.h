@@ -60,7 +60,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]) and "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]) and "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);
@@ -645,6 +645,17 @@ int oodgan_robust_loss_fwd_bwd(const float* img, const float* target, const floa
 int oodgan_robust_loss_fwd_bwd_row(const float* img, const float* target, const float* beta, float* gimg, float* comp, float* part,
                                    float* loss_table, const int* row_dev, int nrows, int B, int C, long HW, int kind, float scale,
                                    int wrt_gen, float grad_mul, void* stream);
+/* Area-pooled view of an image for a loss term of the W+ step (the step takes LPIPS on it with lpips_size).
+ * x, gimg: (BC, H, W) fp32 planes back to back; y, gzero, gs: (BC, H/f, W/f).  f in {2, 4, 8, 16}, H % f == 0, W % f == 0, x / gimg
+ * aligned to 8 (f = 2) or 16 bytes: anything else returns OODGAN_E_ARG with a message and launches nothing.
+ *   oodgan_area_pool_fwd:      y[p] = the mean of the f x f window: summed in fp32 in row-major order, times the exact power of two 1/f^2
+ *                              (F.avg_pool2d(x, f) to within f^2 * 2^-24 * max|x|); gzero, if not NULL, receives 0.0f at every p — the
+ *                              zeroed gradient buffer a term then accumulates into (no fill kernel of another library inside a recorded step).
+ *   oodgan_area_pool_bwd_add:  gimg[., y, x] += gs[., y/f, x/f] * 1/f^2 in place: the exact adjoint of the forward.
+ * One thread owns one pooled pixel and its window in both directions: no atomics, bit-reproducible.  Each accepted call adds one to the
+ * dispatch counter "area_pool". */
+int oodgan_area_pool_fwd(const float* x, float* y, float* gzero, int BC, int H, int W, int f, void* stream);
+int oodgan_area_pool_bwd_add(const float* gs, float* gimg, int BC, int H, int W, int f, void* stream);
 /* torch.optim.Adam step (no weight decay, no amsgrad), step index t>=1 given by the host:
  * anchors: get_optimizer (src/models/OOD_faceGAN_model.py:398-400). */
 int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,

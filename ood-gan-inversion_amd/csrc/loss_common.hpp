@@ -1,4 +1,4 @@
-// What the loss terms of the W+ step share (elementwise.hip: MSE; loss_masked.hip: composite MSE; loss_robust.hip: robust rho; loss_ssim.hip; lpips.hip): every term
+// What the loss terms of the W+ step share (elementwise.hip: MSE; loss_masked.hip: composite MSE; loss_robust.hip: robust rho; loss_ssim.hip; lpips.hip; loss_pool.hip: the pooled view a term may be taken on): every term
 // reduces per-block partial sums to one value per image and writes it either to loss[b] or to a row of the loop's (nrows, B) loss table.
 #pragma once
 #include "common.hpp"

@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 112
+ABI_VERSION = 113
 
 
 class ConvArgs(Structure):
@@ -174,6 +174,8 @@ _SIGS = {
     'oodgan_ssim_loss_fwd_bwd_row': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, P]),
     'oodgan_robust_loss_fwd_bwd': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, c_int, c_float, P]),
     'oodgan_robust_loss_fwd_bwd_row': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_long, c_int, c_float, c_int, c_float, P]),
+    'oodgan_area_pool_fwd': (c_int, [P, P, P, c_int, c_int, c_int, c_int, P]),
+    'oodgan_area_pool_bwd_add': (c_int, [P, P, c_int, c_int, c_int, c_int, P]),
     'oodgan_adam_step': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_int, P]),
     'oodgan_adam_step_dev': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, P]),
     'oodgan_adam_step_dev_sched': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, P]),
@@ -230,7 +232,7 @@ def set_tunable(name, value):
 
 
 def dispatch_count(name):
-    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", or the robust pixel-loss kernel, "robust") since load /
+    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", or the area-pool kernels, "area_pool") since load /
     dispatch_reset() (include/oodgan.h)."""
     n = lib().oodgan_dispatch_count(name.encode())
     if n < 0:

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_noise_seed, check_pixel_loss, check_ssim_weight
+from .engine import WPlusInverter, check_lpips_size, check_noise_seed, check_pixel_loss, check_ssim_weight
 from .modules import Generator
 from .synth import generator_channels
 
@@ -263,7 +263,7 @@ class ood_faceGAN_e4e(nn.Module):
     # ---------------------------------------------------------------- build-defined: W+ refinement
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
-               latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, **kwargs):
+               latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -299,12 +299,19 @@ class ood_faceGAN_e4e(nn.Module):
         |d| = s and s(|d| - s/2) beyond (a very large s is half the MSE), 'geman_mcclure' d^2/2 * s^2/(d^2 + s^2), whose pull on the latent
         goes to zero for an outlier.  The default s = 0.1 is a tenth of the image half-range, about 13 grey levels: a choice, not a measured
         optimum.  ``last_loss_terms['pixel']`` is the term's table whatever its kind; ``['mse']`` is that table for 'mse' and None otherwise.
-        An unknown name, or a scale that is not a finite number > 0, raises ValueError; ``use_graph`` with a robust kind NotImplementedError."""
+        An unknown name, or a scale that is not a finite number > 0, raises ValueError; ``use_graph`` with a robust kind NotImplementedError.
+        ``lpips_size``: the size the LPIPS term is taken at.  None (default): the image's own, the path above unchanged.  An int:
+        the image (the composite where ``loss_region`` selects one) and the target are area-pooled to lpips_size x lpips_size first — mean
+        over f x f windows, f = size / lpips_size in {1, 2, 4, 8, 16} — and the term's gradient comes back through the pool's adjoint; the pixel
+        and SSIM terms stay at full resolution.  256 is the projectors' value (rosinality's projector.py and the StyleGAN2-ADA projector pool
+        to 256² before LPIPS): AlexNet's fields then cover facial structure, and the term costs a fraction of its full-resolution time.
+        A value that is not an int, is below 64, or does not divide the image size by one of those factors raises ValueError."""
         ssim_weight = check_ssim_weight(ssim_weight)
         lr_rampup, lr_rampdown = check_ssim_weight(lr_rampup, 'lr_rampup'), check_ssim_weight(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_ssim_weight(latent_noise, 'latent_noise'), check_ssim_weight(noise_ramp, 'noise_ramp')
         noise_seed, latent_reg = check_noise_seed(noise_seed), check_ssim_weight(latent_reg, 'latent_reg')
         pixel_loss, pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
+        lpips_size = check_lpips_size(lpips_size, int(x.shape[-1]))
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         lats0, enc_feats = self.encode(x, **kwargs)
@@ -333,7 +340,7 @@ class ood_faceGAN_e4e(nn.Module):
         sigma0 = latent_noise * self.generator.latent_std() if latent_noise > 0.0 else 0.0
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
-                            pixel_loss=pixel_loss, pixel_scale=pixel_scale)
+                            pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
                                latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan

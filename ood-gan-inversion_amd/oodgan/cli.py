@@ -27,6 +27,9 @@ Where the W+ loss looks, in the same block:
                                  s(|d| - s/2) beyond, or d^2/2 * s^2/(d^2 + s^2) over the residual d — robust kinds for occluders nobody masked.
     pixel_scale: <s>             their scale in image units ([-1,1] images), a finite number > 0.  Default 0.1, a tenth of the half-range (about
                                  13 grey levels): a choice, not a measured optimum.  huber with a very large s is half the MSE.
+    lpips_size: <int>            the size the LPIPS term (``lpips_weight``) is taken at: the image and the target are area-pooled to
+                                 it first; the projectors' value is 256.  Absent (default): the image's own size.  It must be >= 64 and divide the
+                                 generator size by 1, 2, 4, 8 or 16; anything else is an error.
 The projector schedule of the W+ loop (rosinality's projector.py), in the same block, everything off by default:
 
     lr_rampup, lr_rampdown: <f>  fractions of the run over which the learning rate ramps up linearly / follows a cosine down (projector: 0.05, 0.25)
@@ -50,7 +53,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_noise_seed, check_pixel_loss, check_ssim_weight
+from .engine import check_lpips_size, check_noise_seed, check_pixel_loss, check_ssim_weight
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -147,6 +150,8 @@ def run(opts, wplus_steps=None, log=None):
     ssim_weight = check_ssim_weight(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
     pixel_loss, pixel_scale = check_pixel_loss(inv.get('pixel_loss', 'mse'), inv.get('pixel_scale', 0.1), 'inversion.pixel_loss',
                                                'inversion.pixel_scale')
+    out_size = (opts.get('network_g') or {}).get('out_size')
+    lpips_size = check_lpips_size(inv.get('lpips_size'), out_size if isinstance(out_size, int) else None, 'inversion.lpips_size')
     sched = schedule_options(inv)
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
@@ -166,6 +171,7 @@ def run(opts, wplus_steps=None, log=None):
         from .arch import GraphedForward
         graphed = GraphedForward(model)          # model(x) replayed from a hipGraph: -6 % latency per image at batch 1
     size = model.generator.size
+    check_lpips_size(lpips_size, size, 'inversion.lpips_size')
     summary = {}
     for name, dopt in opts['datasets'].items():
         files, direction = load_files_from_path(dopt, directions_dir)
@@ -184,7 +190,7 @@ def run(opts, wplus_steps=None, log=None):
                 t0 = time.time()
                 if steps > 0:
                     out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
-                                       loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale,
+                                       loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size,
                                        noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), **sched)[0]
                 else:
                     out = (graphed(x) if graphed is not None else model(x))[0]

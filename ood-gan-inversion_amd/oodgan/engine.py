@@ -788,7 +788,9 @@ class _WRun:
         self.lbuf = torch.empty(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32)
         # optional LPIPS(alex) term (oodgan/lpips.py): the target's normalised taps once, a second loss table
         self.lp = inv.lpips if (inv.lpips is not None and inv.lpips_weight != 0.0) else None
-        self.lp_target = self.lp.target_taps(target) if self.lp is not None else None
+        # ``lpips_size``: the term on the area-pooled view, factor ``lp_f``; the pooled target's taps once, outside the step
+        self.lp_f = inv._lpips_f if self.lp is not None else 1
+        self.lp_target = self.lp.target_taps(target if self.lp_f == 1 else ops.area_pool(target.contiguous(), self.lp_f)) if self.lp is not None else None
         self.lp_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if self.lp is not None else None
         # optional SSIM term (csrc/loss_ssim.hip): a third loss table, 1 - SSIM per step and image
         self.ss_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.ssim_weight != 0.0 else None
@@ -837,7 +839,7 @@ class _WRun:
     def _loss_grad(self, img):
         """The loss of the step, each term's values to row dev_t of its table, and gmul * d(sum_b loss_b)/d(img).  The terms in the order
         they accumulate into the gradient: the pixel term (the MSE, or the robust term ``pixel_loss`` names) writes it, LPIPS and 1 - SSIM add
-        lambda * gmul * their part.  With a loss weight beta
+        lambda * gmul * their part; with ``lpips_size`` LPIPS is taken on the area-pooled view of the same image.  With a loss weight beta
         the terms are taken on the composite c: alone, the composite MSE writes beta*dL/dc in one kernel; with LPIPS or
         SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
@@ -851,8 +853,12 @@ class _WRun:
             _, gimg, c = ops.composite_mse_loss_grad(img, self.target, self.beta, gmul, wrt='composite' if on_c else 'gen', composite=on_c,
                                                      table=self.lbuf, row_dev=row)
         x = c if on_c else img
-        if self.lp is not None:
+        if self.lp is not None and self.lp_f == 1:
             self.lp.loss_and_grad(x, gimg, inv.lpips_weight * gmul, table=self.lp_table, row_dev=row, target_taps=self.lp_target)
+        elif self.lp is not None:               # on the pooled view: pool (and zero the small gradient), the term there, unpool-add
+            xs, gs = ops.area_pool(x, self.lp_f, grad_buffer=True)
+            self.lp.loss_and_grad(xs, gs, inv.lpips_weight * gmul, table=self.lp_table, row_dev=row, target_taps=self.lp_target)
+            ops.area_pool_bwd_add(gs, gimg, self.lp_f)
         if self.ss_table is not None:
             ops.ssim_loss_grad(x, self.target, gimg, inv.ssim_weight * gmul, table=self.ss_table, row_dev=row)
         if on_c:
@@ -978,6 +984,24 @@ def check_ssim_weight(value, name='ssim_weight'):
     return w
 
 
+LPIPS_POOL_FACTORS = (1, 2, 4, 8, 16)      # 1: full resolution; the others: the factors of csrc/loss_pool.hip
+LPIPS_MIN_SIZE = 64                         # the smallest size the HIP AlexNet stack is pinned at (tests/test_hip_lpips.py)
+
+
+def check_lpips_size(value, image_size=None, name='lpips_size'):
+    """The size LPIPS is taken at (None: the image's own): ValueError unless it is None or an int (not a bool) >= LPIPS_MIN_SIZE and, once the
+    image size is known, <= it, a divisor of it, with a quotient in LPIPS_POOL_FACTORS.  Returns the value."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f'{name} must be None or an int, got {value!r}')
+    if value < LPIPS_MIN_SIZE:
+        raise ValueError(f'{name} must be >= {LPIPS_MIN_SIZE} (the smallest size the LPIPS stack is checked at), got {value!r}')
+    if image_size is not None and (value > image_size or image_size % value != 0 or image_size // value not in LPIPS_POOL_FACTORS):
+        raise ValueError(f'{name} must divide the image size {image_size} by one of {list(LPIPS_POOL_FACTORS)}, got {value!r}')
+    return value
+
+
 PIXEL_LOSSES = ('mse',) + tuple(ops.ROBUST_KINDS)
 
 
@@ -1009,8 +1033,8 @@ class WPlusInverter:
     ``noise=<list>`` (model.py:483-585), torch.optim.Adam as built by get_optimizer
     (src/models/OOD_faceGAN_model.py:398-400), basicsr MSELoss (losses.py:58-83).
 
-    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight) — + lpips_weight * LPIPS +
-    ssim_weight * (1 - SSIM); the step index is a device counter in every mode (plan, Python-driven, trajectory, any number of streams).
+    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight) — + lpips_weight * LPIPS
+    (with ``lpips_size`` on the image and the target area-pooled to that size) + ssim_weight * (1 - SSIM); the step index is a device counter in every mode (plan, Python-driven, trajectory, any number of streams).
 
     Projector schedule (rosinality's projector.py), every part off by default — the step is then the launch list above:
     ``lr_rampup`` / ``lr_rampdown``: fractions of the run over which the learning rate ramps up linearly / follows a cosine down
@@ -1023,8 +1047,11 @@ class WPlusInverter:
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
-                 pixel_loss='mse', pixel_scale=0.1):
+                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # the size the LPIPS term is taken at: None = the image's own, today's path; an int: the image and the target are
+        # area-pooled to it first (the projectors' value is 256).  The image size is known in ``invert``: the part of the check that needs it runs there
+        self.lpips_size, self._lpips_f = check_lpips_size(lpips_size), 1
         # the pixel term: 'mse' (default: today's kernels and launch list) or a robust rho of the residual with scale ``pixel_scale`` in image
         # units — 'charbonnier', 'huber' (a very large scale: half the MSE), 'geman_mcclure' (DESIGN.md §5).  The default scale 0.1, a tenth of
         # the image half-range (about 13 grey levels), is a choice, not a measured optimum
@@ -1064,6 +1091,8 @@ class WPlusInverter:
         sub-batches, so an image sees the same noise on one stream or several and in any batch.  ``latent_anchor``: (L,512) or (B,L,512),
         what ``latent_reg`` pulls towards (required when latent_reg > 0)."""
         B = w0.shape[0]
+        size = check_lpips_size(self.lpips_size, int(target.shape[-1]))
+        self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
         ids, anchor = self._sched_inputs(w0, noise_ids, latent_anchor)
         if loss_weight is not None:
             if tuple(loss_weight.shape) != (B, 1) + tuple(target.shape[2:]) or loss_weight.dtype != torch.float32 or loss_weight.device != target.device:

@@ -1320,6 +1320,47 @@ def scale_by_plane(g, beta):
     return g
 
 
+def _pool_image(t, name):
+    """t as the area-pool ops take it: a contiguous float32 (B,C,H,W) tensor on the device (no copy is made: the backward updates in place)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f'{name} must be a ROCm (cuda) tensor: the HIP path has no CPU fallback')
+    if t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous float32 (B,C,H,W) tensor, got {t.dtype} {tuple(t.shape)}'
+                         f'{"" if t.is_contiguous() else " (not contiguous)"}')
+    return t
+
+
+def _pool_factor(f):
+    if isinstance(f, bool) or not isinstance(f, int) or f < 1:
+        raise ValueError(f'the pool factor must be a positive int, got {f!r}')
+    return f
+
+
+def area_pool(x, f, grad_buffer=False):
+    """y = the mean of every f x f window of x (B,C,H,W) (oodgan_area_pool_fwd): F.avg_pool2d(x, f), summed in fp32 in row-major
+    order and scaled by the exact 1/f^2.  f in {2, 4, 8, 16} with H % f == 0 and W % f == 0; the library refuses anything else.
+    ``grad_buffer=True`` returns (y, gzero): gzero, of y's shape, zeroed by the same kernel — the buffer a loss term on y accumulates its
+    gradient into before ``area_pool_bwd_add`` (inside a recorded W+ step every fill has to come from this library)."""
+    a, f = _pool_image(x, 'x'), _pool_factor(f)
+    B, C, H, W = a.shape
+    y = torch.empty(B, C, H // f, W // f, device=a.device, dtype=torch.float32)
+    gz = torch.empty_like(y) if grad_buffer else None
+    check(_lib.lib().oodgan_area_pool_fwd(_p(a), _p(y), _p(gz), B * C, H, W, f, _stream()), 'area_pool_fwd')
+    return (y, gz) if grad_buffer else y
+
+
+def area_pool_bwd_add(gs, gimg, f):
+    """gimg (B,C,H,W) += the adjoint of ``area_pool`` applied to gs (B,C,H/f,W/f): every pixel of a window receives gs/f^2, in place
+    (oodgan_area_pool_bwd_add); returns gimg."""
+    g, s, f = _pool_image(gimg, 'gimg'), _pool_image(gs, 'gs'), _pool_factor(f)
+    B, C, H, W = g.shape
+    if tuple(s.shape) != (B, C, H // f, W // f) or s.device != g.device:
+        raise ValueError(f'gs must have shape {(B, C, H // f, W // f)} on {g.device} for gimg {tuple(g.shape)} and factor {f}, got '
+                         f'{tuple(s.shape)} on {s.device}')
+    check(_lib.lib().oodgan_area_pool_bwd_add(_p(s), _p(g), B * C, H, W, f, _stream()), 'area_pool_bwd_add')
+    return gimg
+
+
 def ssim_loss_grad(img, target, gimg=None, grad_mul=1.0, loss_out=None, table=None, row_dev=None):
     """The SSIM term (oodgan_ssim_loss_fwd_bwd): per-image 1 - SSIM(img, target) for (B,C,H,W) float32 images in [-1,1], H, W >= 11
     (``imgio.calculate_ssim`` on the unrounded 127.5*(x+1) images).  ``gimg`` (B,C,H,W), contiguous: gimg += grad_mul * d(sum_b (1 - SSIM_b))/d(img),
