@@ -580,7 +580,8 @@ int oodgan_absmax_scale_clear(float* part, long n, float* out2, void* stream);
 /* loss[b] = mean_{c,p} (img-target)^2 (per image, deterministic), gimg = grad_mul*2*(img-target)/(C*HW).
  * grad_mul is the (power-of-two) loss scale that keeps the back-propagated values O(1) for the split-f16
  * kernels; the caller divides the final latent gradient by it (exact).
- * anchors: basicsr MSELoss (BasicSR/basicsr/losses/losses.py:58-83). part: (B,nparts) scratch. */
+ * anchors: basicsr MSELoss (BasicSR/basicsr/losses/losses.py:58-83). part: (B,nparts) scratch.
+ * The square instantiation of the pixel-term kernels (csrc/loss_pixel.hip), run as one plane of CHW pixels without beta. */
 int oodgan_mse_fwd_bwd(const float* img, const float* target, float* gimg, float* part, float* loss,
                        int B, long CHW, float grad_mul, void* stream);
 int oodgan_mse_nparts(long CHW);
@@ -595,8 +596,8 @@ int oodgan_mse_fwd_bwd_row(const float* img, const float* target, float* gimg, f
  * (BasicSR/basicsr/losses/losses.py:58-83) — the reference's own loop fits the raw G; the composite is this build's objective.
  * d = beta*(img - target); loss[b] = mean_{c,p} d^2 (two-stage partial sums, no float atomics: part (B, oodgan_mse_nparts(C*HW)));
  * gimg = grad_mul*2/(C*HW) * d (the gradient w.r.t. c) or, with wrt_gen = 1, that times beta (w.r.t. img); gimg may be NULL;
- * comp (B,C,HW) or NULL receives c.  beta == 1, C == 3: loss and gimg are bit-identical to oodgan_mse_fwd_bwd.  Counted by the
- * dispatch counter "composite_mse". */
+ * comp (B,C,HW) or NULL receives c.  beta == 1, C == 3: loss and gimg are bit-identical to oodgan_mse_fwd_bwd (the same kernel
+ * templates, csrc/loss_pixel.hip, with beta).  Counted by the dispatch counter "composite_mse". */
 int oodgan_composite_mse_fwd_bwd(const float* img, const float* target, const float* beta, float* gimg, float* comp, float* part,
                                  float* loss, int B, int C, long HW, int wrt_gen, float grad_mul, void* stream);
 /* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
@@ -635,7 +636,8 @@ int oodgan_ssim_nparts(int C, int H, int W);
  * gimg (B,C,HW) or NULL (forward only, the same loss bit for bit) = grad_mul/(C*HW) * psi(d), the gradient w.r.t. c, or with beta and
  * wrt_gen = 1 that times beta (w.r.t. img); comp (B,C,HW) or NULL receives c (needs beta).  A beta = 0 pixel adds the constant rho(0)
  * (s for Charbonnier, else 0) and no gradient; beta == 1 gives the plain form's loss and gimg bit for bit.  part: (B,
- * oodgan_mse_nparts(C*HW)) scratch; two-stage sums, no float atomics: bit-reproducible.  OODGAN_E_ARG with a message for an unknown
+ * oodgan_mse_nparts(C*HW)) scratch; two-stage sums, no float atomics: bit-reproducible (the kernel templates of the MSE entry points with
+ * another rho, csrc/loss_pixel.hip).  OODGAN_E_ARG with a message for an unknown
  * kind and for a scale that is not finite and > 0 with a normal float32 square (about 1.1e-19 < s < 1.8e19).  Counted by the dispatch
  * counter "robust". */
 enum { OODGAN_ROBUST_CHARBONNIER = 1, OODGAN_ROBUST_HUBER = 2, OODGAN_ROBUST_GEMAN_MCCLURE = 3 };

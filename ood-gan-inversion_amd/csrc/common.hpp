@@ -49,7 +49,7 @@ enum { OODGAN_DC_STRIPX = 0, OODGAN_DC_STRIP, OODGAN_DC_S1BIG, OODGAN_DC_S1V2, O
        OODGAN_DC_COMPOSITE_MSE,
        // calls of the SSIM loss kernel (loss_ssim.hip, oodgan_ssim_loss_fwd_bwd[_row])
        OODGAN_DC_SSIM,
-       // calls of the robust pixel-loss kernel (loss_robust.hip, oodgan_robust_loss_fwd_bwd[_row])
+       // calls of the robust pixel-loss kernel (loss_pixel.hip, oodgan_robust_loss_fwd_bwd[_row])
        OODGAN_DC_ROBUST,
        // calls of the area-pool kernels (loss_pool.hip, oodgan_area_pool_fwd / oodgan_area_pool_bwd_add)
        OODGAN_DC_AREA_POOL, OODGAN_DC_COUNT };

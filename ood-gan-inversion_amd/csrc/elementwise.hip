@@ -1,8 +1,8 @@
 // HBM-bound streaming kernels of the generator path: bias+noise+LeakyReLU (fwd/bwd), the merged
-// activation/ToRGB backward, MSE loss + gradient, Adam, and the partial-sum reducer.
+// activation/ToRGB backward, Adam, and the partial-sum reducer.
 // All are float4-vectorised grid-stride loops (16 B/lane, coalesced), one (b,c) row per block-row so
 // the per-channel constants are scalar.
-#include "loss_common.hpp"
+#include "common.hpp"
 
 using namespace oodgan;
 
@@ -201,35 +201,6 @@ __global__ __launch_bounds__(256) void reduce_parts_cols_kernel(const float* __r
     }
 }
 
-// grid: (nparts, B)
-__global__ __launch_bounds__(256) void mse_kernel(const float* __restrict__ img, const float* __restrict__ target,
-                                                  float* __restrict__ gimg, float* __restrict__ part, long CHW, int nparts,
-                                                  float gscale) {
-    __shared__ float red[4];
-    const int b = blockIdx.y;
-    const long base = (long)b * CHW;
-    const long p0 = (long)blockIdx.x * kMseChunk;
-    const long p1 = p0 + kMseChunk < CHW ? p0 + kMseChunk : CHW;
-    float acc = 0.f;
-    if ((CHW & 3) == 0) {
-        for (long i = (p0 >> 2) + threadIdx.x; i < (p1 >> 2); i += 256) {
-            const float4 a = reinterpret_cast<const float4*>(img + base)[i];
-            const float4 t = reinterpret_cast<const float4*>(target + base)[i];
-            float4 d = make_float4(a.x - t.x, a.y - t.y, a.z - t.z, a.w - t.w);
-            acc += d.x * d.x + d.y * d.y + d.z * d.z + d.w * d.w;
-            if (gimg) reinterpret_cast<float4*>(gimg + base)[i] = make_float4(d.x * gscale, d.y * gscale, d.z * gscale, d.w * gscale);
-        }
-    } else {
-        for (long i = p0 + threadIdx.x; i < p1; i += 256) {
-            const float d = img[base + i] - target[base + i];
-            acc += d * d;
-            if (gimg) gimg[base + i] = d * gscale;
-        }
-    }
-    acc = block_sum_256(acc, red);
-    if (threadIdx.x == 0) part[(long)b * nparts + blockIdx.x] = acc;
-}
-
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long n, float beta1, float beta2, float eps,
                                                    float step_size, float inv_bc2_sqrt) {
@@ -380,35 +351,6 @@ extern "C" int oodgan_reduce_parts_cols(const float* part, float* out, int B, in
     hipLaunchKernelGGL(reduce_parts_cols_kernel, dim3((unsigned)(((long)B * C + 3) / 4)), dim3(256), 0, as_stream(stream), part, out, B,
                        C, nparts, out_stride, accumulate);
     return check_launch("reduce_parts_cols");
-}
-
-extern "C" int oodgan_mse_nparts(long CHW) { return (int)((CHW + kMseChunk - 1) / kMseChunk); }
-
-namespace {
-
-int mse_fwd_bwd(const float* img, const float* target, float* gimg, float* part, float* loss, const int* row_dev, int nrows, int B,
-                long CHW, float grad_mul, void* stream) {
-    const int nparts = oodgan_mse_nparts(CHW);
-    hipLaunchKernelGGL(mse_kernel, dim3(nparts, B), dim3(256), 0, as_stream(stream), img, target, gimg, part, CHW, nparts,
-                       grad_mul * 2.0f / (float)CHW);
-    int rc = check_launch("mse");
-    if (rc != OODGAN_OK) return rc;
-    hipLaunchKernelGGL(mean_finish_kernel<>, dim3(B), dim3(64), 0, as_stream(stream), part, loss, nparts, 1.0f / (float)CHW, row_dev, nrows);
-    return check_launch("mse_finish");
-}
-
-}  // namespace
-
-extern "C" int oodgan_mse_fwd_bwd(const float* img, const float* target, float* gimg, float* part, float* loss, int B,
-                                  long CHW, float grad_mul, void* stream) {
-    OODGAN_REQUIRE(img && target && part && loss && B > 0 && CHW > 0, "mse: bad args");
-    return mse_fwd_bwd(img, target, gimg, part, loss, nullptr, 1, B, CHW, grad_mul, stream);
-}
-
-extern "C" int oodgan_mse_fwd_bwd_row(const float* img, const float* target, float* gimg, float* part, float* loss_table,
-                                      const int* row_dev, int nrows, int B, long CHW, float grad_mul, void* stream) {
-    OODGAN_REQUIRE(img && target && part && loss_table && row_dev && nrows > 0 && B > 0 && CHW > 0, "mse_row: bad args");
-    return mse_fwd_bwd(img, target, gimg, part, loss_table, row_dev, nrows, B, CHW, grad_mul, stream);
 }
 
 extern "C" int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2,

@@ -1,11 +1,11 @@
-// What the loss terms of the W+ step share (elementwise.hip: MSE; loss_masked.hip: composite MSE; loss_robust.hip: robust rho; loss_ssim.hip; lpips.hip; loss_pool.hip: the pooled view a term may be taken on): every term
+// What the loss terms of the W+ step share (loss_pixel.hip: MSE, composite MSE, robust rho; loss_ssim.hip; lpips.hip; loss_pool.hip: the pooled view a term may be taken on): every term
 // reduces per-block partial sums to one value per image and writes it either to loss[b] or to a row of the loop's (nrows, B) loss table.
 #pragma once
 #include "common.hpp"
 
 namespace oodgan {
 
-// elements per block of mse_kernel, of the composite and of the robust kernels = elements per partial sum (oodgan_mse_nparts)
+// elements per block of the pixel-term kernels (loss_pixel.hip) = elements per partial sum (oodgan_mse_nparts)
 constexpr int kMseChunk = 16384;
 
 // Offset of the row the losses of B images go to.  row_dev != NULL: row min(row_dev[0], nrows - 1) of a (nrows, B) table — the W+ loop's
@@ -15,8 +15,8 @@ __device__ __forceinline__ long loss_row(const int* __restrict__ row_dev, int nr
     return row_dev ? (long)min(max(row_dev[0], 0), nrows - 1) * B : 0;
 }
 
-// loss[row + b] = (sum of image b's partials) * inv_n: one wave per image, the same order for the MSE and the composite MSE (beta == 1
-// gives the MSE bit for bit).  grid: (B).  A template so that only the units that launch it carry a copy.
+// loss[row + b] = (sum of image b's partials) * inv_n: one wave per image, the same order for every term.  grid: (B).
+// A template so that only the units that launch it carry a copy.
 template <typename T = float>
 __global__ __launch_bounds__(64) void mean_finish_kernel(const T* __restrict__ part, T* __restrict__ loss, int nparts, T inv_n,
                                                          const int* __restrict__ row_dev, int nrows) {

@@ -844,14 +844,8 @@ class _WRun:
         SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
         on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
-        if inv.pixel_loss != 'mse':             # a robust rho(d) in the MSE's place, same flags (csrc/loss_robust.hip)
-            _, gimg, c = ops.robust_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if on_c else 'gen',
-                                              composite=on_c, table=self.lbuf, row_dev=row)
-        elif self.beta is None:
-            _, gimg = ops.mse_loss_grad(img, self.target, gmul, table=self.lbuf, row_dev=row)
-        else:
-            _, gimg, c = ops.composite_mse_loss_grad(img, self.target, self.beta, gmul, wrt='composite' if on_c else 'gen', composite=on_c,
-                                                     table=self.lbuf, row_dev=row)
+        _, gimg, c = ops.pixel_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if on_c else 'gen',
+                                         composite=on_c, table=self.lbuf, row_dev=row)
         x = c if on_c else img
         if self.lp is not None and self.lp_f == 1:
             self.lp.loss_and_grad(x, gimg, inv.lpips_weight * gmul, table=self.lp_table, row_dev=row, target_taps=self.lp_target)

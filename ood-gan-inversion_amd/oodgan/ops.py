@@ -1220,24 +1220,6 @@ def _loss_sink(B, device, loss_out, table, row_dev):
     return loss, None, 1, False, loss
 
 
-def mse_loss_grad(img, target, grad_mul=1.0, loss_out=None, table=None, row_dev=None):
-    """Per-image MSE and its gradient (times grad_mul): (loss[B], gimg).  ``loss_out``: a contiguous float32 (B,) view that receives the losses.
-    ``table`` (nrows, B) + ``row_dev`` (int32[1] on the device): the losses go to row row_dev[0] of the table (oodgan_mse_fwd_bwd_row: the W+
-    loop's loss table, a recorded step writes a new row on every replay); returns (None, gimg)."""
-    a, t = _dev(img, 'img'), _dev(target, 'target')
-    B = a.shape[0]
-    CHW = a.numel() // B
-    L = _lib.lib()
-    part = torch.empty(B, L.oodgan_mse_nparts(CHW), device=a.device, dtype=torch.float32)
-    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
-    g = torch.empty_like(a)
-    if by_row:
-        check(L.oodgan_mse_fwd_bwd_row(_p(a), _p(t), _p(g), _p(part), _p(dst), _p(row), nrows, B, CHW, float(grad_mul), _stream()), 'mse_row')
-    else:
-        check(L.oodgan_mse_fwd_bwd(_p(a), _p(t), _p(g), _p(part), _p(dst), B, CHW, float(grad_mul), _stream()), 'mse')
-    return loss, g
-
-
 def _plane(beta, img, name='beta'):
     """beta (B,1,H,W) float32 on the image's device, one plane per image of ``img`` (B,C,H,W)."""
     w = _dev(beta, name)
@@ -1247,68 +1229,75 @@ def _plane(beta, img, name='beta'):
     return w
 
 
-def composite_mse_loss_grad(img, target, beta, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None, row_dev=None):
-    """The masked objective (oodgan_composite_mse_fwd_bwd): with c = target + beta*(img - target), per-image loss mean((c - target)^2) and its
-    gradient times grad_mul, w.r.t. the generator output (``wrt='gen'``) or w.r.t. the composite (``wrt='composite'``: the LPIPS term adds to it,
-    then ``scale_by_plane`` applies beta).  ``composite=True`` also returns c.  Returns (loss[B] or None with ``table``, gimg, c or None);
-    ``loss_out`` / ``table`` + ``row_dev``: as ``mse_loss_grad``.  beta == 1 gives mse_loss_grad's loss and gradient bit for bit."""
-    a, t = _dev(img, 'img'), _dev(target, 'target')
-    w = _plane(beta, a)
-    if wrt not in ('gen', 'composite'):
-        raise ValueError(f"wrt must be 'gen' or 'composite', got {wrt!r}")
-    B, C, H, W = a.shape
-    L = _lib.lib()
-    part = torch.empty(B, L.oodgan_mse_nparts(C * H * W), device=a.device, dtype=torch.float32)
-    g = torch.empty_like(a)
-    c = torch.empty_like(a) if composite else None
-    gen = 1 if wrt == 'gen' else 0
-    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
-    if by_row:
-        check(L.oodgan_composite_mse_fwd_bwd_row(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), _p(row), nrows, B, C, H * W, gen,
-                                                 float(grad_mul), _stream()), 'composite_mse_row')
-    else:
-        check(L.oodgan_composite_mse_fwd_bwd(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), B, C, H * W, gen, float(grad_mul), _stream()),
-              'composite_mse')
-    return loss, g, c
-
-
 # kinds of the robust pixel term (include/oodgan.h, OODGAN_ROBUST_*)
 ROBUST_KINDS = {'charbonnier': 1, 'huber': 2, 'geman_mcclure': 3}
 
 
-def robust_loss_grad(img, target, kind, scale, beta=None, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None, row_dev=None,
-                     grad=True):
-    """A robust pixel term in place of the MSE (oodgan_robust_loss_fwd_bwd): per-image mean of rho(d), d = img - target or, with a
-    loss weight ``beta`` (B,1,H,W), d = beta*(img - target) on the composite c = target + d.  ``kind``: 'charbonnier' sqrt(d^2 + s^2), 'huber'
-    (d^2/2 up to |d| = s, then s(|d| - s/2); a very large s gives half the MSE) or 'geman_mcclure' (d^2/2 * s^2/(d^2 + s^2)); ``scale``: s > 0, used
-    as a float32.  The gradient is grad_mul/CHW * rho'(d), w.r.t. the composite (``wrt='composite'``) or times beta once more (``wrt='gen'``);
-    ``composite=True`` (needs beta) also returns c; ``grad=False``: forward only, the same loss bit for bit.  Returns (loss[B] or None with
-    ``table``, gimg or None, c or None); ``loss_out`` / ``table`` + ``row_dev``: as ``mse_loss_grad``.  beta == 1 gives the plain form's loss and
-    gradient bit for bit."""
+def pixel_loss_grad(img, target, kind='mse', scale=None, beta=None, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None,
+                    row_dev=None, grad=True):
+    """The pixel term of the W+ loss (csrc/loss_pixel.hip): per-image mean of rho(d), d = img - target or, with a loss weight
+    ``beta`` (B,1,H,W), d = beta*(img - target) on the composite c = target + d (the masked objective).  ``kind``: 'mse' (rho = d^2; the gradient
+    is grad_mul*2/CHW * d) or a robust term at ``scale`` s > 0, used as a float32 (the gradient is grad_mul/CHW * rho'(d)): 'charbonnier'
+    sqrt(d^2 + s^2), 'huber' (d^2/2 up to |d| = s, then s(|d| - s/2); a very large s gives half the MSE) or 'geman_mcclure' (d^2/2 * s^2/(d^2 + s^2)).
+    With beta the gradient is w.r.t. the composite (``wrt='composite'``: LPIPS and SSIM add to it, then ``scale_by_plane`` applies beta) or times
+    beta once more (``wrt='gen'``); ``composite=True`` (needs beta) also returns c; ``grad=False``: forward only, the same loss bit for bit.
+    The plain MSE takes any (B, ...) shape, every other form (B,C,H,W).  Returns (loss[B] or None with ``table``, gimg or None, c or None).
+    ``loss_out``: a contiguous float32 (B,) view that receives the losses.  ``table`` (nrows, B) + ``row_dev`` (int32[1] on the device): the losses
+    go to row row_dev[0] of the table (the ``_row`` entry points: the W+ loop's loss table, a recorded step writes a new row on every replay).
+    One kernel family behind the three entry points: beta == 1 gives the plain form's loss and gradient bit for bit."""
     a, t = _dev(img, 'img'), _dev(target, 'target')
-    if a.dim() != 4 or a.shape != t.shape:
-        raise ValueError(f'robust_loss_grad: img and target must be (B,C,H,W) of one shape, got {tuple(a.shape)} and {tuple(t.shape)}')
-    if kind not in ROBUST_KINDS:
-        raise ValueError(f'kind must be one of {sorted(ROBUST_KINDS)}, got {kind!r}')
+    if kind != 'mse' and kind not in ROBUST_KINDS:
+        raise ValueError(f"kind must be 'mse' or one of {sorted(ROBUST_KINDS)}, got {kind!r}")
+    entry = 'robust_loss' if kind != 'mse' else 'mse' if beta is None else 'composite_mse'
+    if entry != 'mse' and (a.dim() != 4 or a.shape != t.shape):
+        raise ValueError(f'{entry}_grad: img and target must be (B,C,H,W) of one shape, got {tuple(a.shape)} and {tuple(t.shape)}')
     if wrt not in ('gen', 'composite'):
         raise ValueError(f"wrt must be 'gen' or 'composite', got {wrt!r}")
     w = None if beta is None else _plane(beta, a)
     if composite and w is None:
         raise ValueError('composite=True needs beta: without a loss weight the composite is the image')
-    B, C, H, W = a.shape
+    B = a.shape[0]
+    CHW = a.numel() // B
     L = _lib.lib()
-    part = torch.empty(B, L.oodgan_mse_nparts(C * H * W), device=a.device, dtype=torch.float32)
+    part = torch.empty(B, L.oodgan_mse_nparts(CHW), device=a.device, dtype=torch.float32)
     g = torch.empty_like(a) if grad else None
     c = torch.empty_like(a) if composite else None
-    k, gen = ROBUST_KINDS[kind], 1 if wrt == 'gen' else 0
     dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
-    if by_row:
-        check(L.oodgan_robust_loss_fwd_bwd_row(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), _p(row), nrows, B, C, H * W, k, float(scale),
-                                               gen, float(grad_mul), _stream()), 'robust_loss_row')
+    sink = (_p(dst), _p(row), nrows) if by_row else (_p(dst),)
+    if entry == 'mse':
+        args = (_p(a), _p(t), _p(g), _p(part), *sink, B, CHW)
     else:
-        check(L.oodgan_robust_loss_fwd_bwd(_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), _p(dst), B, C, H * W, k, float(scale), gen,
-                                           float(grad_mul), _stream()), 'robust_loss')
+        C = a.shape[1]
+        args = (_p(a), _p(t), _p(w), _p(g), _p(c), _p(part), *sink, B, C, CHW // C)
+        if entry == 'robust_loss':
+            args += (ROBUST_KINDS[kind], float(scale))
+        args += (1 if wrt == 'gen' else 0,)
+    name = entry + ('_row' if by_row else '')
+    check(getattr(L, f'oodgan_{entry}_fwd_bwd' + ('_row' if by_row else ''))(*args, float(grad_mul), _stream()), name)
     return loss, g, c
+
+
+def mse_loss_grad(img, target, grad_mul=1.0, loss_out=None, table=None, row_dev=None):
+    """Per-image MSE and its gradient (times grad_mul): (loss[B], gimg), of any (B, ...) shape; with ``table`` + ``row_dev`` (None, gimg).
+    ``pixel_loss_grad`` with kind 'mse' and no loss weight."""
+    loss, g, _ = pixel_loss_grad(img, target, grad_mul=grad_mul, loss_out=loss_out, table=table, row_dev=row_dev)
+    return loss, g
+
+
+def composite_mse_loss_grad(img, target, beta, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None, row_dev=None):
+    """The masked objective: the MSE on the composite c = target + beta*(img - target); (loss[B] or None with ``table``, gimg, c or None).
+    ``pixel_loss_grad`` with kind 'mse' and the loss weight ``beta``, which it needs."""
+    return pixel_loss_grad(img, target, beta=_dev(beta, 'beta'), grad_mul=grad_mul, wrt=wrt, composite=composite, loss_out=loss_out,
+                           table=table, row_dev=row_dev)
+
+
+def robust_loss_grad(img, target, kind, scale, beta=None, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None, row_dev=None,
+                     grad=True):
+    """A robust pixel term in place of the MSE: ``pixel_loss_grad`` with one of ``ROBUST_KINDS``; (loss[B] or None with ``table``, gimg or None,
+    c or None)."""
+    if kind not in ROBUST_KINDS:
+        raise ValueError(f'kind must be one of {sorted(ROBUST_KINDS)}, got {kind!r}')
+    return pixel_loss_grad(img, target, kind, scale, beta, grad_mul, wrt, composite, loss_out, table, row_dev, grad)
 
 
 def scale_by_plane(g, beta):

@@ -1,4 +1,4 @@
-"""The float64 yardstick of the robust pixel terms of the W+ loss (csrc/loss_robust.hip): rho(d) and psi(d) = rho'(d) for a
+"""The float64 yardstick of the robust pixel terms of the W+ loss (csrc/loss_pixel.hip): rho(d) and psi(d) = rho'(d) for a
 residual d and a scale s, written from the definitions (never from the kernel), in the dtype of ``d`` so that autograd can differentiate
 rho.  tests/test_robust_loss_cpu.py chains them to torch's huber_loss, to the Charbonnier closed form and to autograd."""
 import torch

@@ -1,4 +1,4 @@
-"""Robust pixel terms of the W+ loss (csrc/loss_robust.hip): Charbonnier, Huber and Geman-McClure in the MSE's place.
+"""Robust pixel terms of the W+ loss (csrc/loss_pixel.hip): Charbonnier, Huber and Geman-McClure in the MSE's place.
 
 The kernel against float64 on the same float32 inputs (tests/robust_ref.py) in all of its forms and, with beta == 1, bit for bit against
 its plain form; one W+ step's dL/dW+ against float64 autograd through the oracle; 20 steps against the reference's own autograd loop

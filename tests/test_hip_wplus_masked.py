@@ -1,6 +1,6 @@
 """The masked W+ objective: the loss on the composite c = x + beta*(G(w) - x), beta one (B,1,S,S) plane per image.
 
-Kernels (csrc/loss_masked.hip) against float64 torch and, with beta == 1, bit for bit against the plain MSE kernel; one W+ step's dL/dW+
+Kernels (csrc/loss_pixel.hip, csrc/loss_masked.hip) against float64 torch and, with beta == 1, bit for bit against the plain MSE form; one W+ step's dL/dW+
 against float64 autograd through the oracle (with and without the LPIPS term); beta = 0 pixels have no influence on the run; the
 ``loss_region='blend'`` inversion at 256² against the reference's own autograd loop (tests/golden/make_wplus_masked.py); launch plans,
 streams, the untouched default path and the refusals."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the robust pixel terms (csrc/loss_robust.hip) against the MSE kernels they replace, in ONE process on one GPU.
+"""Cost of the robust pixel terms (csrc/loss_pixel.hip) against the MSE instantiations of the same kernels, in ONE process on one GPU.
 
 Kernels, at B=8, 1024² (the bench geometry), after a warm-up, timed with HIP events over --launches calls per window, the variants
 interleaved over --rounds windows each (a drift of the clock hits every variant alike); median and minimum per call (main kernel + the
