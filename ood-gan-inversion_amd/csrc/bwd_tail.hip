@@ -2,8 +2,10 @@
 // the range-scale checks are all independent of the gradient chain through the feature maps — they only feed the
 // (B, sum Ci) style-gradient accumulator that style_affine_bwd consumes at the very end.  Launched per layer they are
 // ~75 kernels of 5-9 us each per step; here each kind is ONE launch whose job table travels in the kernel arguments.
-// Arithmetic and summation order per output are those of reduce_parts_kernel / demod_bwd_kernel /
-// absmax_scale_check_kernel (autograd of ModulatedConv2d's modulation + demodulation, model.py:236-241).
+// Arithmetic and summation order per output are those of reduce_parts_kernel (row_sum, common.hpp) / demod_bwd_kernel /
+// absmax_scale_check_kernel (autograd of ModulatedConv2d's modulation + demodulation, model.py:236-241).  The per-layer
+// tail reduces with reduce_parts_cols_kernel, whose order is row_sum's only up to 16 partials per row: the batched and
+// the per-layer tail are bit-identical up to that row length, not beyond.
 #include "common.hpp"
 
 using namespace oodgan;

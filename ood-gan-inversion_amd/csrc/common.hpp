@@ -97,7 +97,10 @@ __device__ __forceinline__ float wave_sum(float v) {
     return v;
 }
 
-// Row sums of partials, shared by the per-layer and the batched kernels (they must agree bit for bit: tests/test_hip_generator.py).
+// Row sums of partials.  reduce_parts_kernel (elementwise.hip) and reduce_batch_kernel (bwd_tail.hip) both sum a row with row_sum
+// and agree bit for bit at every length (tests/test_hip_style_tail.py).  reduce_parts_cols_kernel, which the per-layer tail uses, does
+// NOT: its strided loop + wave_sum is the same order only for rows of at most 16 partials (one partial per lane, the butterfly of
+// row_sum16), which is what tests/test_hip_generator.py compares; longer rows differ in the last bits.
 // Loads are unconditional from a clamped index and masked by a select, eight (four) in flight per lane: `for (i = lane; i < n;
 // i += 64) s += p[i]` is one round trip per trip.  n <= 64: 16 lanes per row (row_sum16; every 16-lane group of a wave may own a
 // row of its own); longer rows: the whole wave.

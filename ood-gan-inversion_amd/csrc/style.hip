@@ -13,7 +13,9 @@ namespace {
 // MFMA path: one wave per 16-row tile x 16 batch columns; v_mfma_f32_16x16x4_f32:
 //   A[i=l&15][k=l>>4] = W[r0+i][k], B[k=l>>4][j=l&15] = lat[b0+j][.][k]; each lane loads 16 B of both
 //   operands per 16-deep K step and issues 4 MFMAs (k order inside a step is irrelevant for a sum as long
-//   as A and B agree).  Requires all 16 rows of a tile to read the same latent row.
+//   as A and B agree).  The B operand is one latent row for the whole tile, so a tile whose 16 rows do not all read the
+//   same latent (the wave votes on row_lat[r0 + i]) takes the per-row loop of style_affine_wave_kernel for its 16 batch
+//   columns instead; tiles with one latent keep the MFMA arithmetic.
 __global__ __launch_bounds__(256) void style_affine_mfma_kernel(const float* __restrict__ lat, const float* __restrict__ w,
                                                                 const float* __restrict__ bias, const int* __restrict__ row_lat,
                                                                 float* __restrict__ s, int B, int L, int S, int R, float scale,
@@ -25,6 +27,22 @@ __global__ __launch_bounds__(256) void style_affine_mfma_kernel(const float* __r
     const int b0 = blockIdx.y * 16;
     const int i = lane & 15, kq = lane >> 4;
     const int li = row_lat ? row_lat[r0] : 0;
+    if (row_lat && !__all(row_lat[r0 + i] == li)) {          // wave-uniform branch
+        const int bn = B - b0 < 16 ? B - b0 : 16;
+        for (int q = 0; q < 16; ++q) {
+            const long r = r0 + q;
+            const int lq = row_lat[r];
+            const float bv = bias ? bias[r] * lr_mul : 0.f;
+            for (int b = b0; b < b0 + bn; ++b) {
+                const float* lp = lat + ((long)b * L + lq) * S;
+                float acc = 0.f;
+                for (int k = lane; k < S; k += 64) acc += w[r * S + k] * lp[k];
+                acc = wave_sum(acc);
+                if (lane == 0) s[(long)b * R + r] = acc * scale + bv;
+            }
+        }
+        return;
+    }
     const int bj = b0 + i;
     const float* wp = w + (long)(r0 + i) * S + 4 * kq;
     const float* lp = lat + ((long)(bj < B ? bj : 0) * L + li) * S + 4 * kq;
@@ -218,7 +236,6 @@ __global__ __launch_bounds__(256) void demod_bwd_kernel(const float* __restrict_
 extern "C" int oodgan_style_affine_fwd(const float* latent, const float* wcat, const float* bcat, const int* row_lat, float* s,
                                        int B, int L, int S, int R, float scale, float lr_mul, void* stream) {
     OODGAN_REQUIRE(latent && wcat && s && B > 0 && L > 0 && S > 0 && R > 0, "style_affine_fwd: bad args");
-    // negative S selects the generic path explicitly (per-row latent index not tile-uniform)
     hipStream_t st = as_stream(stream);
     const bool mfma = (R % 16 == 0) && (S % 16 == 0);
     if (mfma)
