@@ -808,6 +808,26 @@ int oodgan_resize_bicubic_ac(const float* x, const float* add, float* y, int pla
 int oodgan_avgpool(const float* x, float* y, int planes, int Hin, int Win, int Hout, int Wout, void* stream);
 int oodgan_resize_bilinear(const float* x, float* y, int planes, int Hin, int Win, int Hout, int Wout, void* stream);
 
+/* ---- the uint8 side of the command-line tool (csrc/imgio.hip; ABI 114).  Stateless, on `stream`, no float atomics. */
+/* File bytes -> network input: bgr uint8 (B,H,W,3) -> out fp32 (B,3,H,W), out[b,c,y,x] = lut[bgr[b,y,x,2-c]].  lut: 256 floats on the device, the
+ * caller's ((k / 255) - 0.5) * 2 evaluated as the host evaluates it (oodgan/imgio.py u8_input_table). */
+int oodgan_u8_to_input(const unsigned char* bgr, const float* lut, float* out, int B, int H, int W, void* stream);
+/* BasicSR tensor2img to uint8 (img_util.py:87-90): t fp32 (B,C,H,W), C in {1,3} -> out uint8 (B,H,W,C), channels reversed when C == 3 and
+ * rgb2bgr != 0.  Per value in float32, lo = (float)vmin, hi = (float)vmax, w = (float)(vmax - vmin):
+ *   u = rint((min(max(t, lo), hi) - lo) / w * 255.0f), ties to even, every operation rounded on its own.  out must be 4-byte aligned.
+ * NaN input is unspecified. */
+int oodgan_tensor2img_u8(const float* t, unsigned char* out, int B, int C, int H, int W, int rgb2bgr, double vmin, double vmax, void* stream);
+/* BasicSR calculate_psnr / calculate_ssim (psnr_ssim.py, test_y_channel=False) of uint8 images a, b (B,H,W,C), C <= 4, with crop_border pixels
+ * removed on every side, up to the closing formulas:
+ *   sse[b]           int64: sum over the cropped region and all channels of (a - b)^2 — exact
+ *   ssim_sum[b, ch]  float64: sum of the SSIM map (11-tap Gaussian window sigma 1.5, the five windowed moments and the map in float64,
+ *                    C1 = (0.01*255)^2, C2 = (0.03*255)^2) over the valid region (H - 2c - 10) x (W - 2c - 10)
+ * part_sse (int64) and part_ssim (float64): workspaces of B * oodgan_psnr_ssim_nparts(C, H, W, crop_border) elements each.  A cropped
+ * side under 11 is OODGAN_E_ARG (nparts 0). */
+int oodgan_psnr_ssim_nparts(int C, int H, int W, int crop_border);
+int oodgan_psnr_ssim_u8(const unsigned char* a, const unsigned char* b, long long* part_sse, double* part_ssim, long long* sse,
+                        double* ssim_sum, int B, int C, int H, int W, int crop_border, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

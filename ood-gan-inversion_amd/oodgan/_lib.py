@@ -5,7 +5,7 @@ RuntimeError is raised (the reference's pybind ops raise RuntimeError from TORCH
 way, src/ops/op/fused_bias_act.cpp:7,13-14)."""
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_long, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_double, c_float, c_int, c_long, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # OODGAN_LIB: load another build of the same ABI (the diagnostic stamp build of tools/clock_probe.py); default = the product
@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 113
+ABI_VERSION = 114
 
 
 class ConvArgs(Structure):
@@ -182,6 +182,10 @@ _SIGS = {
     'oodgan_latent_noise': (c_int, [P, P, P, P, c_int, c_long, c_long, c_int, c_float, c_float, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
+    'oodgan_u8_to_input': (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    'oodgan_tensor2img_u8': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_double, c_double, P]),
+    'oodgan_psnr_ssim_nparts': (c_int, [c_int, c_int, c_int, c_int]),
+    'oodgan_psnr_ssim_u8': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
 }
 
 _lib = None

@@ -39,13 +39,23 @@ The projector schedule of the W+ loop (rosinality's projector.py
                                  ``batch`` or ``streams``
     latent_reg: <lambda>         adds lambda * mean (w - anchor)^2 per image; latent_anchor: start | mean (the start latents of the run, default;
                                  avg_latent + delta_latent)
+Where the host work around a chunk runs, in the same block:
+
+    io: device | host            device (default): files are uploaded as uint8 and converted on the GPU, the inversion, the mask strip, PSNR and
+                                 SSIM are computed there as uint8 / from uint8, the uint8 arrays are downloaded, PNG encoding and writing go to
+                                 ``io_workers`` threads, and the next chunk's files are decoded while the GPU works on this one.  host: every
+                                 step on the calling thread, in numpy.  Same files and the same PSNR either way; SSIM agrees to 1e-9.
+    io_workers: <int>            the threads that encode and write under ``io: device`` (as many again decode ahead): an integer in [1, 16], default 4
+``summary[name]['time']`` is the model call per image; ``summary[name]['wall']`` the data set's whole loop per image, files in to files out.
 ``model_dict`` holds the reference's three variants (run_ood_faceGAN_inversion.py:23-27): the ``network_g`` blocks of
 options/test/{E4E,ReStyle,FeatureStyle}_Face_test.yml resolve unchanged.  LPIPS / identity need third-party weights that
 do not ship: they are reported as skipped."""
 import argparse
+import collections
 import logging
 import os
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -139,9 +149,122 @@ def schedule_options(inv):
     return kw
 
 
+def io_options(inv):
+    """(``inversion.io``, ``inversion.io_workers``), checked.  The worker count is the user's: never derived from the machine's CPU count, which on a
+    shared box says nothing about the CPUs this process may use."""
+    io, workers = inv.get('io', 'device'), inv.get('io_workers', 4)
+    if io not in ('device', 'host'):
+        raise ValueError(f"inversion.io must be 'device' or 'host', got {io!r}")
+    if isinstance(workers, bool) or not isinstance(workers, int) or not 1 <= workers <= 16:
+        raise ValueError(f'inversion.io_workers must be an integer in [1, 16], got {workers!r}')
+    return io, workers
+
+
+class WriterPool:
+    """``workers`` threads for the PIL / numpy side of a chunk (PNG encode + write, host metrics): ``submit`` hands a call over and blocks while
+    2 * workers are in flight, ``drain`` waits for all of them and returns their results in submission order.  A worker's exception is raised
+    from the ``submit`` or ``drain`` that collects it; leaving the ``with`` block cancels what has not started and joins the threads.
+    The tasks must not touch HIP or torch-ROCm: the library's calls belong to the thread that owns the stream."""
+
+    def __init__(self, workers):
+        self.limit = 2 * workers
+        self.max_pending = 0                    # the most tasks that were in flight at once
+        self._executor = ThreadPoolExecutor(max_workers=workers, thread_name_prefix='oodgan-io')
+        self._pending, self._results = collections.deque(), []
+
+    def submit(self, fn, *args):
+        while len(self._pending) >= self.limit:
+            self._results.append(self._pending.popleft().result())
+        self._pending.append(self._executor.submit(fn, *args))
+        self.max_pending = max(self.max_pending, len(self._pending))
+
+    def drain(self):
+        while self._pending:
+            self._results.append(self._pending.popleft().result())
+        results, self._results = self._results, []
+        return results
+
+    def close(self):
+        self._executor.shutdown(wait=True, cancel_futures=True)
+        self._pending.clear()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def postprocess_host(out, x, aligns, files, bgrs, size, save_dir, metrics, metric_opts):
+    """``io: host`` — a chunk's outputs on the calling thread: per file the inversion and the mask strip as uint8 (``tensor2img``), written, and
+    the metrics against the file (its own pixels when it is size x size, else the uint8 of ``x``).  Returns (metrics, inversions, strips)."""
+    results, strips = [], []
+    for k, (f, bgr) in enumerate(zip(files, bgrs)):
+        res = imgio.tensor2img(out[k:k + 1], rgb2bgr=True, min_max=(-1, 1))
+        imgio.imwrite(os.path.join(save_dir, 'inversion', os.path.basename(f)), res)
+        gt = bgr if bgr.shape[:2] == (size, size) else imgio.tensor2img(x[k:k + 1], rgb2bgr=True, min_max=(-1, 1)).astype(np.float64)
+        metrics = evaluate(gt, res, metrics, metric_opts)
+        masks = imgio.extract_masks(aligns, size, index=k)
+        if masks is not None:
+            imgio.imwrite(os.path.join(save_dir, 'masks', os.path.basename(f)), masks)
+        results.append(res)
+        strips.append(masks)
+    return metrics, results, strips
+
+
+def _host_metric(kind, gt, res, opt):
+    fn = imgio.calculate_psnr if kind == 'psnr' else imgio.calculate_ssim
+    return kind, fn(gt, res, crop_border=opt['crop_border'], test_y_channel=opt['test_y_channel'])
+
+
+def postprocess_device(out, x, aligns, files, bgrs, size, save_dir, metrics, metric_opts, pool):
+    """``io: device`` — the same outputs with the arithmetic on the GPU (oodgan/imgio.py, device counterparts): the calling thread converts the
+    chunk to uint8, takes PSNR / SSIM there, downloads the uint8 arrays and hands each file's encode + write to ``pool``.  ``bgrs``: the files
+    as uint8 BGR, host arrays or device tensors.  A metric with test_y_channel runs as the host function on a worker; its value arrives with
+    ``collect_host_metrics(pool.drain(), metrics)``.  Returns (metrics, inversions, strips) — host arrays, (B,size,size,3) and (B,size,size*n) or None."""
+    if metrics is None:
+        metrics = {'psnr': [], 'ssim': [], 'lpips': [], 'identity': []}
+    opt = {k: v for k, v in (metric_opts or {}).items() if k in ('psnr', 'ssim') and v}
+    res = imgio.tensor2img_device(out, rgb2bgr=True, min_max=(-1, 1))
+    strips = imgio.extract_masks_device(aligns, size)
+    gt = None
+    if opt:
+        own = [tuple(b.shape[:2]) == (size, size) for b in bgrs]
+        gt = torch.empty_like(res) if all(own) else imgio.tensor2img_device(x, rgb2bgr=True, min_max=(-1, 1))
+        for k, b in enumerate(bgrs):
+            if own[k]:
+                gt[k].copy_(torch.as_tensor(b))
+        on_device = {k: v for k, v in opt.items() if not v['test_y_channel']}
+        for crop in sorted({v['crop_border'] for v in on_device.values()}):
+            psnr, ssim = imgio.psnr_ssim_device(gt, res, crop)
+            for kind, values in (('psnr', psnr), ('ssim', ssim)):
+                if kind in on_device and on_device[kind]['crop_border'] == crop:
+                    metrics[kind] += values
+    res = res.cpu().numpy()
+    strips = None if strips is None else strips.cpu().numpy()
+    luma = {k: v for k, v in opt.items() if v['test_y_channel']}
+    gt = gt.cpu().numpy() if luma else None
+    for k, f in enumerate(files):
+        pool.submit(imgio.imwrite, os.path.join(save_dir, 'inversion', os.path.basename(f)), res[k])
+        if strips is not None:
+            pool.submit(imgio.imwrite, os.path.join(save_dir, 'masks', os.path.basename(f)), strips[k])
+        for kind, v in luma.items():
+            pool.submit(_host_metric, kind, gt[k], res[k], v)
+    return metrics, res, strips
+
+
+def collect_host_metrics(results, metrics):
+    """Appends the (kind, value) results of the pool's metric tasks to ``metrics`` — submission order is file order."""
+    for r in results:
+        if r is not None:
+            metrics[r[0]].append(r[1])
+    return metrics
+
+
 def run(opts, wplus_steps=None, log=None):
     log = log or logging.getLogger('oodgan.cli')
     inv = opts.get('inversion') or {}
+    io, io_workers = io_options(inv)
     loss_region, mask_dir = inv.get('loss_region', 'full'), inv.get('mask_dir')
     if loss_region not in ('full', 'blend'):
         raise ValueError(f"inversion.loss_region must be 'full' or 'blend', got {loss_region!r}")
@@ -181,34 +304,48 @@ def run(opts, wplus_steps=None, log=None):
         # ``inversion.batch`` files per call (default 1 = the reference's per-file loop, run_ood_faceGAN_inversion.py:158-182): images are
         # independent on this path, and the W+ loop of one image leaves most of the GPU idle (284 ms per image alone, 131 ms in a batch of 8)
         nb = max(1, int(inv.get('batch', 1)))
-        for c0 in range(0, len(files), nb):
-            chunk = files[c0:c0 + nb]
-            bgrs = [imgio.imread(f).astype(np.float64) for f in chunk]
-            x = torch.cat([imgio.image_to_input(bgr, size, device='cuda') for bgr in bgrs], 0)
-            region = load_loss_weights(chunk, mask_dir, size).cuda() if (mask_dir and steps > 0) else loss_region
-            with torch.no_grad():
-                t0 = time.time()
-                if steps > 0:
-                    out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
-                                       loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size,
-                                       noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), **sched)[0]
+        chunks = [files[c0:c0 + nb] for c0 in range(0, len(files), nb)]
+        wall0 = time.time()
+        with WriterPool(io_workers) as pool, ThreadPoolExecutor(max_workers=io_workers, thread_name_prefix='oodgan-read') as reader:
+            # io: device — the next chunk's files are decoded by ``reader`` while the GPU works on this one
+            ahead = [reader.submit(imgio.imread, f) for f in chunks[0]] if (io == 'device' and chunks) else None
+            for ci, chunk in enumerate(chunks):
+                c0 = ci * nb
+                if io == 'device':
+                    bgrs = [torch.from_numpy(t.result()).cuda() for t in ahead]
+                    ahead = [reader.submit(imgio.imread, f) for f in chunks[ci + 1]] if ci + 1 < len(chunks) else None
+                    if len({tuple(b.shape) for b in bgrs}) == 1:
+                        x = imgio.input_from_u8(torch.stack(bgrs), size)
+                    else:
+                        x = torch.cat([imgio.input_from_u8(bgr, size) for bgr in bgrs], 0)
                 else:
-                    out = (graphed(x) if graphed is not None else model(x))[0]
-                torch.cuda.synchronize()
-                times += [(time.time() - t0) / len(chunk)] * len(chunk)
-            for k, (f, bgr) in enumerate(zip(chunk, bgrs)):
-                res = imgio.tensor2img(out[k:k + 1], rgb2bgr=True, min_max=(-1, 1))
-                imgio.imwrite(os.path.join(save_dir, 'inversion', os.path.basename(f)), res)
-                gt = bgr if bgr.shape[:2] == (size, size) else imgio.tensor2img(x[k:k + 1], rgb2bgr=True, min_max=(-1, 1)).astype(np.float64)
-                metrics = evaluate(gt, res, metrics, opts.get('metrics'))
-                masks = imgio.extract_masks(model.aligns, size, index=k)
-                if masks is not None:
-                    imgio.imwrite(os.path.join(save_dir, 'masks', os.path.basename(f)), masks)
+                    bgrs = [imgio.imread(f).astype(np.float64) for f in chunk]
+                    x = torch.cat([imgio.image_to_input(bgr, size, device='cuda') for bgr in bgrs], 0)
+                region = load_loss_weights(chunk, mask_dir, size).cuda() if (mask_dir and steps > 0) else loss_region
+                with torch.no_grad():
+                    t0 = time.time()
+                    if steps > 0:
+                        out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
+                                           loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size,
+                                           noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), **sched)[0]
+                    else:
+                        out = (graphed(x) if graphed is not None else model(x))[0]
+                    torch.cuda.synchronize()
+                    times += [(time.time() - t0) / len(chunk)] * len(chunk)
+                if io == 'device':
+                    metrics = postprocess_device(out, x, model.aligns, chunk, bgrs, size, save_dir, metrics, opts.get('metrics'), pool)[0]
+                else:
+                    metrics = postprocess_host(out, x, model.aligns, chunk, bgrs, size, save_dir, metrics, opts.get('metrics'))[0]
+            done = pool.drain()                 # every file is written (or its worker's exception raised) before the summary is logged
+            if metrics is not None:
+                collect_host_metrics(done, metrics)
+        wall = (time.time() - wall0) / max(len(files), 1)
         model.delta_latent.data -= direction.cuda()
         mean = lambda v: float(np.mean(v)) if v else float('nan')
-        summary[name] = dict(n=len(files), time=mean(times), psnr=mean((metrics or {}).get('psnr')),
+        summary[name] = dict(n=len(files), time=mean(times), wall=wall, psnr=mean((metrics or {}).get('psnr')),
                              ssim=mean((metrics or {}).get('ssim')))
         log.info('Average process time of %s: %f', name, summary[name]['time'])
+        log.info('Average wall time per image of %s (files in to files out): %f', name, summary[name]['wall'])
         log.info('Average PSNR of %s: %f', name, summary[name]['psnr'])
         log.info('Average SSIM of %s: %f', name, summary[name]['ssim'])
         for skipped in ('lpips', 'identity'):

@@ -163,3 +163,110 @@ def _ssim(a, b):
 def calculate_ssim(img, img2, crop_border, input_order='HWC', test_y_channel=False, **kwargs):
     a, b = _prepare(img, img2, crop_border, input_order, test_y_channel)
     return float(np.mean([_ssim(a[..., i], b[..., i]) for i in range(a.shape[2])]))
+
+
+# ----------------------------------------------------------------------------------------------- device counterparts
+# The same conversions and metrics on the GPU (csrc/imgio.hip), for the CLI's `inversion.io: device`: tensors in, tensors
+# out, every kernel on the current stream.  The functions above stay the yardstick (tests/test_hip_imgio_device.py).
+_U8_TABLES = {}
+
+
+def u8_input_table():
+    """The 256 values ``image_to_input`` / ``img2tensor`` can produce, by their own expression: entry k is the network input of byte k."""
+    return ((torch.arange(256, dtype=torch.float64) / 255.0).float() - 0.5) * 2
+
+
+def _u8_dev(t, name, device=None):
+    """A contiguous uint8 device tensor from a uint8 ndarray or tensor (uploaded to ``device`` when it is on the host)."""
+    if isinstance(t, np.ndarray):
+        if t.dtype != np.uint8:
+            raise TypeError(f'{name} must be uint8, got {t.dtype}')
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    if not torch.is_tensor(t) or t.dtype != torch.uint8:
+        raise TypeError(f'{name} must be a uint8 array or tensor, got {type(t).__name__} {getattr(t, "dtype", "")}')
+    if not t.is_cuda:
+        if device is None:
+            raise RuntimeError(f'{name} must be a ROCm (cuda) tensor: the HIP path has no CPU fallback')
+        t = t.to(device)
+    return t.contiguous()
+
+
+def input_from_u8(bgr_u8, size=1024, device='cuda'):
+    """``image_to_input`` from the file's bytes: (H,W,3) or (B,H,W,3) uint8 BGR (ndarray or tensor; a host array is uploaded as uint8) ->
+    (B,3,size,size) float32 RGB in [-1,1] on the device, bit for bit the host's values (a table of its 256 results, ``oodgan_u8_to_input``);
+    resized like ``image_to_input`` when the width is not ``size``."""
+    from . import _lib, samm
+    from .ops import _p, _stream
+    u = _u8_dev(bgr_u8, 'bgr_u8', device)
+    if u.dim() == 3:
+        u = u.unsqueeze(0)
+    if u.dim() != 4 or u.shape[3] != 3 or u.numel() == 0:
+        raise ValueError(f'bgr_u8 must be (H,W,3) or (B,H,W,3), got {tuple(u.shape)}')
+    lut = _U8_TABLES.get(u.device)
+    if lut is None:
+        lut = _U8_TABLES[u.device] = u8_input_table().to(u.device)
+    B, H, W, _ = u.shape
+    x = torch.empty(B, 3, H, W, device=u.device, dtype=torch.float32)
+    _lib.check(_lib.lib().oodgan_u8_to_input(_p(u), _p(lut), _p(x), B, H, W, _stream()), 'u8_to_input')
+    if x.shape[-1] != size:
+        x = samm.resize_bilinear(x, size)
+    return x
+
+
+def tensor2img_device(t, rgb2bgr=True, min_max=(0, 1)):
+    """``tensor2img`` to uint8 on the device (``oodgan_tensor2img_u8``): (B,C,H,W) float32, C in {1,3} -> uint8 (B,H,W,3), BGR when
+    ``rgb2bgr``, or (B,H,W) for C = 1; byte for byte what ``tensor2img`` gives for each batch item."""
+    from . import _lib
+    from .ops import _dev, _p, _stream
+    t = _dev(t, 'tensor')
+    if t.dim() != 4 or t.shape[1] not in (1, 3) or t.numel() == 0:
+        raise ValueError(f'tensor must be (B,C,H,W) with C in (1, 3), got {tuple(t.shape)}')
+    B, C, H, W = t.shape
+    out = torch.empty((B, H, W, C) if C == 3 else (B, H, W), device=t.device, dtype=torch.uint8)
+    _lib.check(_lib.lib().oodgan_tensor2img_u8(_p(t), _p(out), B, C, H, W, 1 if rgb2bgr else 0, float(min_max[0]), float(min_max[1]),
+                                               _stream()), 'tensor2img_u8')
+    return out
+
+
+def extract_masks_device(aligns, size=1024):
+    """``extract_masks`` for the whole batch, on the device: the (B, size, size*n) uint8 mask strips (None on any failure, like it)."""
+    try:
+        from . import samm
+        return tensor2img_device(samm.extract_masks(aligns, size), min_max=(0, 1))
+    except Exception:
+        return None
+
+
+def psnr_ssim_device(gt_u8, res_u8, crop_border):
+    """``calculate_psnr`` / ``calculate_ssim`` (test_y_channel=False) of uint8 device images (B,H,W,C) or (B,H,W): two lists of B float64
+    values.  The device returns the exact integer sum of squared differences and the float64 sums of the SSIM maps
+    (``oodgan_psnr_ssim_u8``); the closing formulas are the host functions' own.  Synchronises (one small download)."""
+    from . import _lib
+    from .ops import _p, _stream
+    a, b = _u8_dev(gt_u8, 'gt_u8'), _u8_dev(res_u8, 'res_u8')
+    if a.shape != b.shape:
+        raise ValueError(f'Image shapes are different: {tuple(a.shape)}, {tuple(b.shape)}.')
+    if a.dim() == 3:
+        a, b = a.unsqueeze(3), b.unsqueeze(3)
+    if a.dim() != 4 or a.numel() == 0:
+        raise ValueError(f'images must be (B,H,W,C) or (B,H,W), got {tuple(a.shape)}')
+    B, H, W, C = a.shape
+    crop = int(crop_border)
+    hc, wc = H - 2 * crop, W - 2 * crop
+    if crop < 0 or hc < 11 or wc < 11:
+        raise ValueError(f'SSIM needs a cropped image of at least 11x11, got {H}x{W} with crop_border {crop_border}')
+    L = _lib.lib()
+    nparts = L.oodgan_psnr_ssim_nparts(C, H, W, crop)
+    part_sse = torch.empty(B * nparts, device=a.device, dtype=torch.int64)
+    part_ssim = torch.empty(B * nparts, device=a.device, dtype=torch.float64)
+    sse = torch.empty(B, device=a.device, dtype=torch.int64)
+    ssim_sum = torch.empty(B, C, device=a.device, dtype=torch.float64)
+    _lib.check(L.oodgan_psnr_ssim_u8(_p(a), _p(b), _p(part_sse), _p(part_ssim), _p(sse), _p(ssim_sum), B, C, H, W, crop, _stream()),
+               'psnr_ssim_u8')
+    sse, ssim_sum = sse.cpu().numpy(), ssim_sum.cpu().numpy()
+    psnr, ssim = [], []
+    for i in range(B):
+        mse = np.float64(sse[i]) / (hc * wc * C)
+        psnr.append(float('inf') if mse == 0 else float(20.0 * np.log10(255.0 / np.sqrt(mse))))
+        ssim.append(float(np.mean(ssim_sum[i] / ((hc - 10) * (wc - 10)))))
+    return psnr, ssim
