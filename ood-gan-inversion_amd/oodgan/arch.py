@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_lpips_size, check_noise_seed, check_pixel_loss, check_ssim_weight
+from .engine import WPlusInverter, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
 from .modules import Generator
 from .synth import generator_channels
 
@@ -306,10 +306,10 @@ class ood_faceGAN_e4e(nn.Module):
         and SSIM terms stay at full resolution.  256 is the projectors' value (rosinality's projector.py and the StyleGAN2-ADA projector pool
         to 256² before LPIPS): AlexNet's fields then cover facial structure, and the term costs a fraction of its full-resolution time.
         A value that is not an int, is below 64, or does not divide the image size by one of those factors raises ValueError."""
-        ssim_weight = check_ssim_weight(ssim_weight)
-        lr_rampup, lr_rampdown = check_ssim_weight(lr_rampup, 'lr_rampup'), check_ssim_weight(lr_rampdown, 'lr_rampdown')
-        latent_noise, noise_ramp = check_ssim_weight(latent_noise, 'latent_noise'), check_ssim_weight(noise_ramp, 'noise_ramp')
-        noise_seed, latent_reg = check_noise_seed(noise_seed), check_ssim_weight(latent_reg, 'latent_reg')
+        ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
+        lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
+        latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
+        noise_seed, latent_reg = check_noise_seed(noise_seed), check_nonneg(latent_reg, 'latent_reg')
         pixel_loss, pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
         lpips_size = check_lpips_size(lpips_size, int(x.shape[-1]))
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):

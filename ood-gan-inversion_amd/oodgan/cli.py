@@ -63,7 +63,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_lpips_size, check_noise_seed, check_pixel_loss, check_ssim_weight
+from .engine import check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -141,7 +141,7 @@ def evaluate(gt_bgr, res_bgr, metrics, opt):
 def schedule_options(inv):
     """The projector-schedule keywords of ``model.invert`` from the ``inversion`` block, checked (ValueError names the option)."""
     defaults = dict(lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, latent_reg=0.0)
-    kw = {k: check_ssim_weight(inv.get(k, d), f'inversion.{k}') for k, d in defaults.items()}
+    kw = {k: check_nonneg(inv.get(k, d), f'inversion.{k}') for k, d in defaults.items()}
     kw['noise_seed'] = check_noise_seed(inv.get('noise_seed', 0), 'inversion.noise_seed')
     kw['latent_anchor'] = inv.get('latent_anchor', 'start')
     if kw['latent_anchor'] not in ('start', 'mean'):
@@ -270,7 +270,7 @@ def run(opts, wplus_steps=None, log=None):
         raise ValueError(f"inversion.loss_region must be 'full' or 'blend', got {loss_region!r}")
     if mask_dir and loss_region != 'full':
         raise ValueError('inversion.mask_dir and inversion.loss_region: blend exclude each other')
-    ssim_weight = check_ssim_weight(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
+    ssim_weight = check_nonneg(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
     pixel_loss, pixel_scale = check_pixel_loss(inv.get('pixel_loss', 'mse'), inv.get('pixel_scale', 0.1), 'inversion.pixel_loss',
                                                'inversion.pixel_scale')
     out_size = (opts.get('network_g') or {}).get('out_size')

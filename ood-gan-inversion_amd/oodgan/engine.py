@@ -165,10 +165,9 @@ class GeneratorEngine:
             rgb(f'to_rgbs.{j}', cout, res, i + 2)
             cin, i = cout, i + 2
         self.layers = layers
-        # fused backward producers (csrc/bwd_producers.hip): per-layer range scale carried from one W+ step to the next;
+        # fused backward producers (csrc/bwd_producers.hip): per-layer range scale carried from one W+ step to the next (_new_run_state);
         # the flags below exist for the exact-scale fallback and for A/B tests (tests flip them on the instance)
         self.fused_bwd = True
-        self.bwd_state, self.bwd_flag = {}, None
         styled = [L for L in layers if L.kind != 'rgb']
         self.layers_styled_last = styled[-1]
         self.fused_fwd = True
@@ -231,28 +230,35 @@ class GeneratorEngine:
         self.row_layer = torch.tensor(row_layer, dtype=torch.int32, device=dev)
         self.drow_layer = torch.tensor(drow_layer, dtype=torch.int32, device=dev)
         self.n_styled = sidx
-        # forward range control of the split-f16 path (ops.FwdRange): per-step state, created for the batch size in use
-        self.fwd_range = None
         self.carry_range = True      # False: every forward measures its scales exactly (the fallback after a violation)
         self.stored_noises = [g(f'noises.noise_{k}') for k in range(self.num_layers)] if (prefix + 'noises.noise_0') in state else None
-        self.saved = None
+        # ConstantInput broadcast over the batch, one copy per (batch size, stream): prepared data like the weights, shared between clones
+        # (clones are made per inversion and must not make the copies again)
+        self._const_b = {}
+        self._new_run_state()
+
+    def _new_run_state(self):
+        """Everything a run of this engine writes, in one place: what ``clone_shared`` must not share.  A state attribute created anywhere
+        else would silently be shared between the sub-batches of two HIP streams."""
+        self.saved = None                           # forward(save=True) -> backward: activations, styles, demodulation factors
+        self._fwd_serial = 0                        # forwards counted: backward() refuses activations a later forward may have overwritten
+        self.bwd_state, self.bwd_flag = {}, None    # backward range scale per layer, carried from one W+ step to the next; their sticky flag
+        # forward range control of the split-f16 path (ops.FwdRange): one state per batch size, ``fwd_range`` the one in use
+        self.fwd_range, self._ranges = None, {}
+        self.last_gs = None                         # dL/dstyles of the last backward, kept for inspection
 
     def clone_shared(self):
-        """A second engine over the SAME prepared weights (read-only) with its own per-step state."""
+        """A second engine over the SAME prepared weights (read-only) with its own per-run state."""
         import copy
         e = copy.copy(self)
-        e.saved = None
-        e.bwd_state, e.bwd_flag = {}, None
-        e.fwd_range = None
-        e._ranges = {}
+        e._new_run_state()
         return e
 
     def reset_fwd_state(self, B=None):
         """Forget the carried forward range scales (new images / new batch): the next forward measures them exactly.
         Every batch size's state is reset (``B``: only that one) — a state left `valid` with another image set's scales would
         make the first forward at that batch size run in carry mode and the result depend on the call history."""
-        ranges = self.__dict__.get('_ranges', {})
-        todo = list(ranges.values()) if B is None else [r for r in (ranges.get(B),) if r is not None]
+        todo = list(self._ranges.values()) if B is None else [r for r in (self._ranges.get(B),) if r is not None]
         if self.fwd_range is not None and (B is None or self.fwd_range.B == B) and not any(r is self.fwd_range for r in todo):
             todo.append(self.fwd_range)
         for r in todo:
@@ -268,12 +274,11 @@ class GeneratorEngine:
         if self.fwd_range is None or self.fwd_range.B != B:
             # one state per batch size (an inversion alternates between the sub-batch of the W+ loop and the full batch of the OOD forward:
             # the latter's carried scales survive the former)
-            ranges = self.__dict__.setdefault('_ranges', {})
-            r = ranges.get(B)
+            r = self._ranges.get(B)
             if r is None:
                 # never evicted: captured hipGraphs (arch.GraphedForward, the W+ step graphs) hold raw pointers to a state's
                 # q / vm / flag / s_sc / d_sc — a state is ~100 KB per batch size
-                r = ranges[B] = ops.FwdRange(self.n_styled, B, self.R, self.DR, self.row_layer, self.drow_layer, self.device)
+                r = self._ranges[B] = ops.FwdRange(self.n_styled, B, self.R, self.DR, self.row_layer, self.drow_layer, self.device)
             self.fwd_range = r
         return self.fwd_range
 
@@ -310,7 +315,7 @@ class GeneratorEngine:
         B = latent.shape[0]
         # forwards are counted: the activations saved for backward() live in pooled scratch buffers (ops.sform_scratch: keyed by shape and
         # stream) and their S-form scales alias the range state — ANY later forward of this engine on the same stream may overwrite them
-        self._fwd_serial = getattr(self, '_fwd_serial', 0) + 1
+        self._fwd_serial += 1
         s_all = self.styles(latent)
         d_all = torch.empty(B, self.DR, device=self.device, dtype=torch.float32)
         if self.batched_tail:       # the demodulation factors of all styled convs in one launch
@@ -347,11 +352,10 @@ class GeneratorEngine:
         acts = {}
         # ConstantInput broadcast over the batch (model.py:296-305): read-only, one copy per batch size — not a torch copy kernel per forward
         # (a launch plan, oodgan_plan_*, replays this library's launches only)
-        cache = self.__dict__.setdefault('_const_b', {})
         ck = (B, ops._stream_handle())      # per stream: the copy is enqueued on the stream that first needs it
-        x = cache.get(ck)
+        x = self._const_b.get(ck)
         if x is None:
-            x = cache[ck] = self.const_input.expand(B, -1, -1, -1).contiguous()
+            x = self._const_b[ck] = self.const_input.expand(B, -1, -1, -1).contiguous()
         acts['input'] = x
         skip, out = None, x
         pending = None
@@ -544,7 +548,7 @@ class GeneratorEngine:
         sv = self.saved
         if sv is None:
             raise RuntimeError('backward() without forward(save=True)')
-        if sv.get('serial') != getattr(self, '_fwd_serial', None):
+        if sv['serial'] != self._fwd_serial:
             raise RuntimeError('backward(): another forward of this engine ran after forward(save=True) — the saved activations (pooled S-form / F-form '
                                'buffers, scales of the range state) may have been overwritten; call backward() right after the forward it belongs to')
         acts, s_all, d_all, noises, B = sv['acts'], sv['s_all'], sv['d_all'], sv['noises'], sv['B']
@@ -757,8 +761,9 @@ def _flag_stream(device):
 
 class _WRun:
     """One (sub-)batch of the W+ loop on one HIP stream, advanced one step per ``advance()``.  A step is forward, ``_loss_grad`` (the one
-    place that knows the loss terms), backward, Adam; its step index lives on the device (``dev_t``), so every step — driven from Python or
-    replayed from a launch plan — is the same launch list.
+    place that knows the loss terms), backward, Adam; its step index lives on the device (``dev_t``), so every step is the same launch
+    list, ``_eager_step``, however it is run.  ``replay`` says how: None — every step from Python; 'plan' — recorded into a launch plan
+    (oodgan_plan_*) while it runs, then one oodgan_plan_run call per step; 'graph' — captured into a hipGraph and replayed (``_record``).
 
     Range guard (round 6): the carried forward / backward range scales raise sticky device flags when a tensor's range
     moved by more than the format's head-room within one step (range control).  Until round 5 the flags were read after the last
@@ -766,13 +771,14 @@ class _WRun:
     two flags are copied to pinned host memory on a side stream behind an event of the compute stream — no synchronisation of the compute
     stream; ``check_lag`` steps later (the copy has long finished: the host runs ahead of the GPU) the host looks at them.  Clear: the
     snapshot becomes the last clean state.  Set: the run goes back to the last clean state, repeats that window (<= check_every steps)
-    with exact scales, and continues in carry mode from freshly measured scales.
+    with exact scales, and continues in carry mode from freshly measured scales.  A captured step cannot change its arithmetic mid-run: a
+    graph run has no guard, ``WPlusInverter._invert_runs`` reads the flags once at its end and repeats a flagged inversion through the guard.
 
     Projector schedule: the learning-rate factor, the latent noise and its strength are functions of ``dev_t`` (and of the
     run's constants: seed, image ids, ``steps``) evaluated inside the kernels — a rollback, which restores (w, m, v, t), needs nothing new: a
     repeated window draws the same noise and takes the same learning rates."""
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, beta=None, ids=None, anchor=None):
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -795,7 +801,7 @@ class _WRun:
         # optional SSIM term (csrc/loss_ssim.hip): a third loss table, 1 - SSIM per step and image
         self.ss_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.ssim_weight != 0.0 else None
         # projector schedule (csrc/wplus_sched.hip).  ``w_in``, the perturbed latent the generator reads, is a persistent
-        # buffer like ``w``: born inside a recorded step it would be carved out of blocks the step's temporaries held (see ``use_plan`` below)
+        # buffer like ``w``: born inside a recorded step it would be carved out of blocks the step's temporaries held (see ``replay`` below)
         self.ids = ids
         self.w_in = torch.empty_like(self.w) if inv.latent_noise != 0.0 else None
         # latent prior: latent_reg * mean (w - anchor)^2 per image, a fourth loss table; the anchor is constant for the run
@@ -803,7 +809,7 @@ class _WRun:
         self.lat_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.latent_reg != 0.0 else None
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
-        self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0
+        self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
         self.clean = (0, self.w.clone(), None, None) if self.guard else None     # m = v = 0 at t = 0
         self.pending, self.exact_until = None, 0
         self.steps_run = 0                                       # forward/backward pairs enqueued, repeated windows included
@@ -816,9 +822,12 @@ class _WRun:
         # that temporaries of the same step held earlier, and on every replay those temporaries' kernels would write over them — borders
         # included (seen as NaN from the second replay on).  The third step is RECORDED while it runs (oodgan_plan_*, under a private
         # allocator pool so that every buffer it touched keeps its address); every later step is one oodgan_plan_run call instead of ~100
-        # ctypes calls and the Python between them
-        self.use_plan = bool(inv.use_plan) and not keep_traj and eng.sform     # the trajectory's per-step w.clone() is a torch kernel outside the plan
-        self.plan, self.pool, self.eager_left, self.plan_steps, self.plan_size = None, None, 2, 0, 0
+        # ctypes calls and the Python between them.  A hipGraph is captured under a pool of its own, which no step before it has touched:
+        # there the second step is the captured one
+        if replay == 'plan' and (keep_traj or not eng.sform):       # the trajectory's per-step w.clone() is a torch kernel outside the plan
+            replay = None
+        self.replay, self.warmup = replay, 1 if replay == 'graph' else 2
+        self.plan, self.pool, self.eager_left, self.plan_steps, self.plan_size = None, None, self.warmup, 0, 0
 
     # ---- one W+ step on the current stream
     def _eager_step(self):
@@ -859,18 +868,30 @@ class _WRun:
             ops.scale_by_plane(gimg, self.beta)
         return gimg
 
-    def _step(self):
-        eng = self.eng
-        if self.plan is not None:
-            self.plan.run()
-            self.plan_steps += 1
-        elif (self.use_plan and self.eager_left == 0 and not self.exact_until and eng.fused_bwd and eng.carry_range
-              and self.steps - self.t >= 3):
+    def _record(self):
+        """Perform the step and keep it in ``self.plan``: a launch plan, recorded while the step runs, or a captured hipGraph."""
+        if self.replay == 'graph':
+            self.stream.synchronize()
+            self.plan = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.plan, stream=self.stream):
+                self._eager_step()
+            self.inv._graphs.append(self.plan)      # replays are still in flight when ``invert`` returns
+            self.plan.replay()                      # a capture only captures
+        else:
             plan, pool = ops.LaunchPlan(), _plan_pool(self.w.device, self.w.shape[0])
             with torch.cuda.use_mem_pool(pool):
                 with plan.recording():
                     self._eager_step()
             self.plan, self.pool, self.plan_size = plan, pool, plan.size
+
+    def _step(self):
+        eng = self.eng
+        if self.plan is not None:
+            self.plan.replay() if self.replay == 'graph' else self.plan.run()
+            self.plan_steps += 1
+        elif self.replay and self.eager_left == 0 and (self.replay == 'graph' or (
+                not self.exact_until and eng.fused_bwd and eng.carry_range and self.steps - self.t >= 3)):
+            self._record()
         else:
             self._eager_step()
             self.eager_left = max(0, self.eager_left - 1)
@@ -930,7 +951,7 @@ class _WRun:
         eng.reset_bwd_state()                                    # the next step measures its scales exactly, like the first of a run
         eng.reset_fwd_state()
         self.exact_until = 0
-        self.eager_left = 2
+        self.eager_left = self.warmup
         self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone())
 
     def _advance(self):
@@ -950,11 +971,8 @@ class _WRun:
         """Enqueue the next step (or resolve a check / roll back); False once the run is complete and verified."""
         if self.done():
             return False
-        if self.stream is None:
+        with torch.cuda.stream(self.stream):        # None: the caller's stream
             self._advance()
-        else:
-            with torch.cuda.stream(self.stream):
-                self._advance()
         return not self.done()
 
     def done(self):
@@ -967,8 +985,8 @@ class _WRun:
         self.pool = None
 
 
-def check_ssim_weight(value, name='ssim_weight'):
-    """The weight of the SSIM loss term (or another option of that kind: ``name``) as a float; ValueError unless it is a finite number >= 0."""
+def check_nonneg(value, name='ssim_weight'):
+    """The option ``name`` (a loss weight, a ramp fraction, a noise strength) as a float; ValueError unless it is a finite number >= 0."""
     try:
         w = float(value)
     except (TypeError, ValueError):
@@ -976,6 +994,9 @@ def check_ssim_weight(value, name='ssim_weight'):
     if not (math.isfinite(w) and w >= 0.0):
         raise ValueError(f'{name} must be a finite number >= 0, got {value!r}')
     return w
+
+
+check_ssim_weight = check_nonneg       # the name it had while the SSIM weight was its only caller
 
 
 LPIPS_POOL_FACTORS = (1, 2, 4, 8, 16)      # 1: full resolution; the others: the factors of csrc/loss_pool.hip
@@ -1028,7 +1049,9 @@ class WPlusInverter:
     (src/models/OOD_faceGAN_model.py:398-400), basicsr MSELoss (losses.py:58-83).
 
     The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight) — + lpips_weight * LPIPS
-    (with ``lpips_size`` on the image and the target area-pooled to that size) + ssim_weight * (1 - SSIM); the step index is a device counter in every mode (plan, Python-driven, trajectory, any number of streams).
+    (with ``lpips_size`` on the image and the target area-pooled to that size) + ssim_weight * (1 - SSIM); the step index is a device counter in every mode.
+    The step itself is defined once too, ``_WRun._eager_step``: run from Python, replayed from a launch plan (default) or, with
+    ``invert(use_graph=True)``, from a captured hipGraph, with a trajectory or without, on any number of streams.
 
     Projector schedule (rosinality's projector.py), every part off by default — the step is then the launch list above:
     ``lr_rampup`` / ``lr_rampdown``: fractions of the run over which the learning rate ramps up linearly / follows a cosine down
@@ -1037,7 +1060,8 @@ class WPlusInverter:
     ``latent_reg``: adds latent_reg * mean (w - latent_anchor)^2 per image, evaluated at the unperturbed w (``last_terms['latent']``).
 
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
-    {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}."""
+    {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
+    {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
@@ -1057,15 +1081,15 @@ class WPlusInverter:
         self.lpips, self.lpips_weight = lpips, float(lpips_weight)
         # + ssim_weight * (1 - SSIM): the metric the CLI reports, on the unrounded images; 0 (default) = the term, its
         # kernel launches and its table do not exist
-        self.ssim_weight = check_ssim_weight(ssim_weight)
-        self.lr_rampup, self.lr_rampdown = check_ssim_weight(lr_rampup, 'lr_rampup'), check_ssim_weight(lr_rampdown, 'lr_rampdown')
-        self.latent_noise, self.noise_ramp = check_ssim_weight(latent_noise, 'latent_noise'), check_ssim_weight(noise_ramp, 'noise_ramp')
-        self.noise_seed, self.latent_reg = check_noise_seed(noise_seed), check_ssim_weight(latent_reg, 'latent_reg')
+        self.ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
+        self.lr_rampup, self.lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
+        self.latent_noise, self.noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
+        self.noise_seed, self.latent_reg = check_noise_seed(noise_seed), check_nonneg(latent_reg, 'latent_reg')
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
         self.check_every, self.check_lag = int(check_every), max(0, int(check_lag))
-        self._runs, self._pins = [], []
+        self._runs, self._pins, self._graphs = [], [], []
         self.last_stats = self.last_plan = None
         self.on_step = None         # optional callable(run) after every enqueued step (progress reporting; tests inject faults with it)
 
@@ -1093,8 +1117,6 @@ class WPlusInverter:
                 raise ValueError(f'loss_weight must be a float32 {(B, 1) + tuple(target.shape[2:])} tensor on {target.device}, got '
                                  f'{loss_weight.dtype} {tuple(loss_weight.shape)} on {loss_weight.device}')
             loss_weight = loss_weight.contiguous()
-            if use_graph:
-                raise NotImplementedError('use_graph with a loss weight: use the launch plans (default) instead')
         streams = max(1, min(int(streams), B))
         if B == 0:          # an empty shard (oodgan/parallel.py hands a rank with no images an empty batch): nothing to launch
             steps = 0
@@ -1105,21 +1127,30 @@ class WPlusInverter:
         if return_trajectory:
             streams, use_graph = 1, False
         if use_graph:
-            return self._invert_graph(target, w0, noises, steps, streams)
-        if streams == 1:
-            return self._invert_runs(target, w0, noises, steps, 1, return_trajectory, loss_weight, ids, anchor)
+            self._refuse_graph(loss_weight)
         from . import _lib
-        # the multi-stream threshold of the 8-wave stride-1 kernel, unless the caller set the tunable itself; the value that was read is
-        # the one restored
-        old = _lib.lib().oodgan_get_tunable(b's1_big_min_items')
-        override = old == _S1_BIG_DEFAULT and MULTI_STREAM_S1_BIG_MIN_ITEMS != _S1_BIG_DEFAULT
+        # the multi-stream threshold of the 8-wave stride-1 kernel, unless the caller set the tunable itself; not for a graph run
+        override = (streams > 1 and not use_graph and MULTI_STREAM_S1_BIG_MIN_ITEMS != _S1_BIG_DEFAULT
+                    and _lib.lib().oodgan_get_tunable(b's1_big_min_items') == _S1_BIG_DEFAULT)
         if override:
             _lib.set_tunable('s1_big_min_items', MULTI_STREAM_S1_BIG_MIN_ITEMS)
         try:
-            return self._invert_runs(target, w0, noises, steps, streams, False, loss_weight, ids, anchor)
+            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor)
         finally:
             if override:
-                _lib.set_tunable('s1_big_min_items', old)
+                _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
+
+    def _refuse_graph(self, loss_weight):
+        """What the hipGraph option does not take, refused before anything is launched.  (Since the graph replays ``_WRun._eager_step`` these
+        are no longer things it cannot express; lifting them is a change of its own.)"""
+        for on, what in ((loss_weight is not None, 'a loss weight'),
+                         (self.lpips is not None and self.lpips_weight != 0.0, 'the LPIPS term'),
+                         (self.ssim_weight != 0.0, 'the SSIM term'),
+                         (self.pixel_loss != 'mse', 'a robust pixel term'),
+                         (self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0,
+                          'the projector schedule (lr ramps, latent noise, latent prior)')):
+            if on:
+                raise NotImplementedError(f'use_graph with {what}: use the launch plans (default) instead')
 
     def _sched_inputs(self, w0, noise_ids, latent_anchor):
         """(ids, anchor) of a call: the noise ids (None when the noise is off) and the prior's anchor (None when the prior is off), checked."""
@@ -1139,11 +1170,13 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, ids=None, anchor=None):
-        """(side streams, engines, [(target, w0, noises, beta, ids, anchor)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams)."""
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams).
+        ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
+        caller's own."""
         B = w0.shape[0]
         cur = torch.cuda.current_stream()
-        side = _side_streams(w0.device, streams)
+        side = _side_streams(w0.device, streams) if on_side else [None]
         # the state resets enqueue zero-fills on the CALLER's stream: they must precede the wait_stream below, or nothing
         # orders them against the atomicOr / atomic max the side streams do on the same flags (engines[0] keeps its
         # FwdRange and bwd_flag across calls)
@@ -1158,38 +1191,37 @@ class WPlusInverter:
                           [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous(),
                           None if ids is None else ids[sl].contiguous(),
                           anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor))
-        for st in side:
-            st.wait_stream(cur)                 # AFTER the slices above were enqueued on the caller's stream
+        if on_side:
+            for st in side:
+                st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
         return side, engines, parts
 
     @staticmethod
     def _gather(side, w, tables):
         """The per-stream latents (joined along the batch) and loss tables (``tables``: one list per term, None = term off; joined along the
-        images) on the caller's stream."""
+        images) on the caller's stream; of a single run, its own tensors."""
         cur = torch.cuda.current_stream()
+        join = lambda ts, dim: ts[0] if len(ts) == 1 else torch.cat(ts, dim)
         for st in side:
-            cur.wait_stream(st)
-        out = [torch.cat(w, 0)] + [None if ts[0] is None else torch.cat(ts, 1) for ts in tables]
+            if st is not None:
+                cur.wait_stream(st)
+        out = [join(w, 0)] + [None if ts[0] is None else join(ts, 1) for ts in tables]
         for ts in [w] + tables:                 # tensors produced on side streams are consumed on the caller's stream
             for t in ts:
                 if t is not None:
                     t.record_stream(cur)
         return out
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, beta=None, ids=None, anchor=None):
-        self._runs = []
-        if streams == 1:
-            eng = self.engine
-            eng.reset_bwd_state()
-            eng.reset_fwd_state()
-            runs = [_WRun(self, eng, target, w0, noises, steps, None, return_trajectory, beta, ids, anchor)]
-        else:
-            side, engines, parts = self._split(target, w0, noises, beta, streams, ids, anchor)
-            runs = []
-            for i, st in enumerate(side):
-                with torch.cuda.stream(st):         # state tensors initialised on the stream that uses them
-                    runs.append(_WRun(self, engines[i], parts[i][0], parts[i][1], parts[i][2], steps, st, False, *parts[i][3:]))
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None):
+        self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
+        replay = 'graph' if use_graph else 'plan' if self.use_plan else None
+        # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor)
+        runs = []
         try:
+            for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):
+                with torch.cuda.stream(st):     # state tensors initialised on the stream that uses them
+                    runs.append(_WRun(self, eng, x, w, nz, steps, st, return_trajectory, replay, *rest))
             busy = True
             while busy:
                 busy = False
@@ -1198,74 +1230,21 @@ class WPlusInverter:
         finally:
             for r in runs:
                 r.close()
+            # the runs point back here: left in ``_runs`` they make the inverter, with the graphs it keeps, a reference cycle, which the
+            # collector frees whenever it happens to run — inside the next inverter's capture, where destroying a graph aborts the process
+            self._runs = []
         self.last_stats = {'steps_run': [r.steps_run for r in runs], 'rollbacks': [r.rollbacks for r in runs]}
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
-        if streams == 1:
-            r = runs[0]
-            losses = self._total(r.lbuf, r.lp_table, r.ss_table, r.lat_table)
-            return (r.w, losses, r.traj) if return_trajectory else (r.w, losses)
-        w, mse, lp, ss, lat = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
-                                                                       [r.lat_table for r in runs]])
-        return w, self._total(mse, lp, ss, lat)
+        w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
+                                                             [r.lat_table for r in runs]])
+        # a graph run has no per-window guard: its flags are read once, here, and a flagged inversion is repeated through the guarded loop
+        if use_graph and any(eng.bwd_scale_violated() or eng.fwd_range_violated() for eng in engines):
+            return self.invert(target, w0, noises, steps, streams=streams, use_graph=False)
+        losses = self._total(*tables)
+        return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
     def _total(self, mse, lp, ss=None, lat=None):
         self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         return total if lat is None else total + self.latent_reg * lat
-
-    def _invert_graph(self, target, w0, noises, steps, streams):
-        """hipGraph replay of one captured W+ step per stream (measured 3 % slower than eager launches on this host; kept as an
-        option).  A replayed step cannot change its arithmetic mid-run: the range flags are read at the end and a flagged inversion is
-        repeated eagerly (with the per-window guard)."""
-        if self.lpips is not None and self.lpips_weight != 0.0:
-            raise NotImplementedError('use_graph with the LPIPS term: use the launch plans (default) instead')
-        if self.ssim_weight != 0.0:
-            raise NotImplementedError('use_graph with the SSIM term: use the launch plans (default) instead')
-        if self.pixel_loss != 'mse':
-            raise NotImplementedError('use_graph with a robust pixel term: use the launch plans (default) instead')
-        if self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0:
-            raise NotImplementedError('use_graph with the projector schedule (lr ramps, latent noise, latent prior): use the launch plans (default) instead')
-        side, engines, split = self._split(target, w0, noises, None, streams)
-        gmul = ops.loss_scale_for(target.numel() // w0.shape[0])
-        dev = w0.device
-        parts = []
-        for i, st in enumerate(side):
-            with torch.cuda.stream(st):             # state tensors initialised on the stream that uses them
-                w = split[i][1].clone()
-                parts.append(dict(target=split[i][0], w=w, noises=split[i][2], m=torch.zeros_like(w), v=torch.zeros_like(w),
-                                  t=torch.zeros(1, dtype=torch.int32, device=dev),
-                                  lbuf=torch.empty(steps, w.shape[0], device=dev, dtype=torch.float32)))
-
-        def one_step(pr, eng):
-            img = eng.forward(pr['w'], pr['noises'], save=True, range_mode='carry')
-            loss, gimg = ops.mse_loss_grad(img, pr['target'], gmul)
-            g = eng.backward(gimg, gmul, carry_scale=True)
-            ops.adam_step_dev(pr['w'], g, pr['m'], pr['v'], pr['t'], self.lr, self.betas, self.eps)
-            return loss
-
-        for i, st in enumerate(side):       # step 1 eagerly (also warms allocator pools / scratch buffers of every stream) ...
-            with torch.cuda.stream(st):
-                parts[i]['lbuf'][0].copy_(one_step(parts[i], engines[i]))
-        graphs = [None] * streams
-        if steps > 1:
-            # ... then ONE W+ step is captured per stream into a hipGraph and replayed
-            for i, st in enumerate(side):
-                st.synchronize()
-                gph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gph, stream=st):
-                    parts[i]['lstat'] = one_step(parts[i], engines[i])
-                graphs[i] = gph
-        for t in range(2, steps + 1):
-            for i, st in enumerate(side):
-                with torch.cuda.stream(st):
-                    graphs[i].replay()
-                    parts[i]['lbuf'][t - 1].copy_(parts[i]['lstat'])
-        w, losses = self._gather(side, [pr['w'] for pr in parts], [[pr['lbuf'] for pr in parts]])
-        for eng in engines:
-            eng.saved = None
-        self._graphs = graphs               # keep the graphs (and their private pools) alive until the next call
-        self.last_stats = {'steps_run': [steps] * streams, 'rollbacks': [0] * streams}
-        if any(eng.bwd_scale_violated() or eng.fwd_range_violated() for eng in engines):
-            return self.invert(target, w0, noises, steps, False, streams, False)
-        return w, losses

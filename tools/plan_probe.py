@@ -39,7 +39,7 @@ def make_run(torch, eng, target, w0, noises, WPlusInverter, _WRun, use_plan, ste
     eng.reset_bwd_state()
     eng.reset_fwd_state()
     inv._runs = []
-    run = _WRun(inv, eng, target, w0, noises, steps, None, False)
+    run = _WRun(inv, eng, target, w0, noises, steps, None, False, 'plan' if use_plan else None)
     for _ in range(3):              # exact step, recorded step, one replay / one more eager step
         run.advance()
     torch.cuda.synchronize()
