@@ -687,6 +687,25 @@ int oodgan_latent_prior_fwd_bwd(const float* w, const float* a, float* g, float*
 /* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
 int oodgan_latent_prior_fwd_bwd_row(const float* w, const float* a, float* g, float* loss_table, const int* row_dev, int nrows, int B,
                                     long n, int a_batched, float weight, void* stream);
+/* oodgan_latent_noise with the draws repeated every `period` elements: element e takes the draw oodgan_latent_noise makes for element
+ * e mod period (the W mode of the loop: one 512-vector of noise for all layers, as the projector's W mode repeats its noise).  period must
+ * be a multiple of 4 and divide n_per_image (else -1); period == n_per_image: the bits of oodgan_latent_noise. */
+int oodgan_latent_noise_tied(const float* w, float* w_in, const long* ids, const int* t_dev, int B, long n_per_image, long period, long seed,
+                             int total_steps, float sigma0, float noise_ramp, void* stream);
+/* Latent controls of the W+ loop: the latent side of a step in place of oodgan_adam_step_dev_sched, for w, g, m, v (B, L, D).
+ * Increments t_dev[0] first (t), then per image, one block each:
+ *   d_le = w_le - mean_l w_le (the mean from a double sum) and R_b = mean_le d_le^2 (double sum, rounded once), written to row
+ *   min(t - 1, nrows - 1) of delta_table (nrows, B) — the zero-based step; delta_table NULL: not written;
+ *   delta_reg > 0: g_le += 2 delta_reg / (L D) * d_le (the gradient of delta_reg * R_b; the cross terms cancel: sum_l d_le = 0);
+ *   tied != 0: g_le = (float) sum_l (double) g_le, in layer order, for every l (the gradient of a (B, D) leaf expanded over the layers);
+ *   g is written back wherever one of the two changed it: it holds what Adam consumed;
+ *   Adam as oodgan_adam_step_dev_sched with the step size (float)((double)lr * (double)layer_lr[l] * r(t - 1) / (1 - beta1^t)); layer_lr
+ *   (L floats on the device) NULL: no factor.  A factor 0 leaves that layer's w bit-unchanged (its moments still move).
+ * delta_table NULL, delta_reg 0, tied 0 and layer_lr NULL or all 1: w, m, v, t bit-identical to oodgan_adam_step_dev_sched.  This R is the
+ * squared spread of the layers about their mean, the symmetric form; e4e's own regulariser measures the distance from layer 0. */
+int oodgan_latent_step(float* w, float* g, float* m, float* v, int B, int L, int D, float lr, float beta1, float beta2, float eps,
+                       int* t_dev, int total_steps, float rampup, float rampdown, const float* layer_lr, float delta_reg, int tied,
+                       float* delta_table, int nrows, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

@@ -180,6 +180,9 @@ _SIGS = {
     'oodgan_adam_step_dev': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, P]),
     'oodgan_adam_step_dev_sched': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, P]),
     'oodgan_latent_noise': (c_int, [P, P, P, P, c_int, c_long, c_long, c_int, c_float, c_float, P]),
+    'oodgan_latent_noise_tied': (c_int, [P, P, P, P, c_int, c_long, c_long, c_long, c_int, c_float, c_float, P]),
+    'oodgan_latent_step': (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, P, c_float,
+                                   c_int, P, c_int, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
     'oodgan_u8_to_input': (c_int, [P, P, P, c_int, c_int, c_int, P]),

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
+from .engine import WPlusInverter, check_latent_controls, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
 from .modules import Generator
 from .synth import generator_channels
 
@@ -263,7 +263,8 @@ class ood_faceGAN_e4e(nn.Module):
     # ---------------------------------------------------------------- build-defined: W+ refinement
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
-               latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, **kwargs):
+               latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
+               delta_reg=0.0, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -305,7 +306,20 @@ class ood_faceGAN_e4e(nn.Module):
         over f x f windows, f = size / lpips_size in {1, 2, 4, 8, 16} — and the term's gradient comes back through the pool's adjoint; the pixel
         and SSIM terms stay at full resolution.  256 is the projectors' value (rosinality's projector.py and the StyleGAN2-ADA projector pool
         to 256² before LPIPS): AlexNet's fields then cover facial structure, and the term costs a fraction of its full-resolution time.
-        A value that is not an int, is below 64, or does not divide the image size by one of those factors raises ValueError."""
+        A value that is not an int, is below 64, or does not divide the image size by one of those factors raises ValueError.
+        ``edit``: an editing direction applied AFTER the fit — a float32 (L,512), (1,L,512) or (B,L,512) tensor on the model's
+        device.  The loop runs exactly as without it (the same ``losses``, the same refined latents w); the final OOD forward is taken at w + edit
+        and the returned ``lats`` are those latents, the ones the output was generated from.  ``self.last_refined_lats`` holds w after every call,
+        with an edit or without.  (A direction in ``delta_latent`` is part of the START latents instead: the loop then fits the unedited input
+        from an edited start and works the edit off again.)  A wrong shape, dtype or device raises ValueError.
+        Latent controls of the loop, off by default.  ``latent_space``: 'w+' (every layer its own vector) or 'w': one vector
+        per image, started at the layer mean of the start latents and kept on every layer — the most editable, least faithful end of e4e's
+        editability-distortion trade-off; the latent noise is then one vector repeated over the layers.  ``layer_lr``: L finite factors >= 0 of
+        ``lr``, one per layer; 0 freezes a layer (e.g. fit the coarse layers only).  ``delta_reg`` = lambda >= 0 adds lambda * mean_le
+        (w_le - mean_l w_le)^2 per image, the squared spread of the layers about their mean — the symmetric, build-defined form (e4e's own
+        regulariser measures the distance from layer 0); W is its lambda -> infinity limit.  ``last_loss_terms['delta']`` is its table (None
+        when off).  'w' together with ``layer_lr`` or ``delta_reg``, a wrong length, a negative or a non-finite entry raise ValueError;
+        ``use_graph`` with any of the three NotImplementedError."""
         ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
         lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
@@ -314,8 +328,10 @@ class ood_faceGAN_e4e(nn.Module):
         lpips_size = check_lpips_size(lpips_size, int(x.shape[-1]))
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
+        latent_space, layer_lr, delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg, self.generator.n_latent)
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
+        edit = self._check_edit(edit, lats0)
         if noise is None:
             noise = [n.expand(B, -1, -1, -1).contiguous() for n in self.generator.make_noise()]
         beta = self._loss_weight(loss_region, x, lats0, enc_feats, noise)
@@ -340,12 +356,14 @@ class ood_faceGAN_e4e(nn.Module):
         sigma0 = latent_noise * self.generator.latent_std() if latent_noise > 0.0 else 0.0
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
-                            pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size)
+                            pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
+                            delta_reg=delta_reg)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
                                latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise')}
-        out, lats = self._ood_forward(x, w, enc_feats, noise=noise, **kw)
+        self.last_refined_lats = w
+        out, lats = self._ood_forward(x, w if edit is None else (w + edit).contiguous(), enc_feats, noise=noise, **kw)
         # An inversion returns finished results.  Without this the host runs ahead into the next inversion's set-up while the device still works
         # on this one: blocks this inversion's side streams freed are then not yet reusable, the caching allocator goes to the driver for new ones
         # and every inversion pays ~20 ms (measured, bench.py back-to-back inversions on one box: 1054-1061 ms without, 1036-1047 ms with it —
@@ -353,6 +371,18 @@ class ood_faceGAN_e4e(nn.Module):
         # carried-scale flag in Generator.forward happened to provide this synchronisation)
         torch.cuda.current_stream().synchronize()
         return out, lats, losses
+
+    @staticmethod
+    def _check_edit(edit, lats0):
+        """``invert(edit=...)``: None, or a float32 (L,512) / (1,L,512) / (B,L,512) tensor on the latents' device (ValueError otherwise)."""
+        if edit is None:
+            return None
+        B, L, D = lats0.shape
+        if (not isinstance(edit, torch.Tensor) or tuple(edit.shape) not in ((L, D), (1, L, D), (B, L, D)) or edit.dtype != torch.float32
+                or edit.device != lats0.device):
+            got = f'{edit.dtype} {tuple(edit.shape)} on {edit.device}' if isinstance(edit, torch.Tensor) else repr(edit)
+            raise ValueError(f'edit must be a float32 {(L, D)}, {(1, L, D)} or {(B, L, D)} tensor on {lats0.device}, got {got}')
+        return edit.detach()
 
     def _loss_weight(self, loss_region, x, lats0, enc_feats, noise):
         """beta of ``invert(loss_region=...)``: None for 'full'; for 'blend' the mask of one hooked generator pass at the start latents

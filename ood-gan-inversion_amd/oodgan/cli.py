@@ -39,6 +39,17 @@ The projector schedule of the W+ loop (rosinality's projector.py
                                  ``batch`` or ``streams``
     latent_reg: <lambda>         adds lambda * mean (w - anchor)^2 per image; latent_anchor: start | mean (the start latents of the run, default;
                                  avg_latent + delta_latent)
+Edits and the latent controls of the W+ loop, in the same block:
+
+    edit: start | final          where a data set's ``editing`` direction goes when the loop runs.  start (default): into ``delta_latent``, as the
+                                 reference does for the plain forward — the loop then fits the unedited input from edited start latents and
+                                 works the edit off again (logged once as a warning).  final: the loop runs on the unedited latents and the
+                                 direction is added to the refined latents for the final forward (``invert(edit=...)``).  Without W+ steps both
+                                 are the reference's ``delta_latent += direction``.
+    latent_space: w+ | w         w+ (default): every layer its own vector.  w: one 512-vector per image, started at the layer mean.
+    layer_lr: [f, ...]           one factor >= 0 of ``lr`` per generator layer (18 at 1024²); 0 freezes a layer.  Not with ``latent_space: w``.
+    delta_reg: <lambda>          adds lambda * the squared spread of the layers about their mean per image (the symmetric form of e4e's
+                                 regulariser, which measures from layer 0).  Default 0 = off.  Not with ``latent_space: w``.
 Where the host work around a chunk runs, in the same block:
 
     io: device | host            device (default): files are uploaded as uint8 and converted on the GPU, the inversion, the mask strip, PSNR and
@@ -63,7 +74,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
+from .engine import check_latent_controls, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -147,6 +158,21 @@ def schedule_options(inv):
     if kw['latent_anchor'] not in ('start', 'mean'):
         raise ValueError(f"inversion.latent_anchor must be 'start' or 'mean', got {kw['latent_anchor']!r}")
     return kw
+
+
+def latent_options(inv, n_layers=None):
+    """The latent-control keywords of ``model.invert`` from the ``inversion`` block, checked (ValueError names the option); ``n_layers``: the
+    generator's layer count once the model exists."""
+    space, rates, reg = check_latent_controls(inv.get('latent_space', 'w+'), inv.get('layer_lr'), inv.get('delta_reg', 0.0), n_layers, 'inversion.')
+    return dict(latent_space=space, layer_lr=None if rates is None else list(rates), delta_reg=reg)
+
+
+def edit_option(inv):
+    """``inversion.edit``: 'start' (default) or 'final'; anything else raises ValueError."""
+    edit = inv.get('edit', 'start')
+    if edit not in ('start', 'final'):
+        raise ValueError(f"inversion.edit must be 'start' or 'final', got {edit!r}")
+    return edit
 
 
 def io_options(inv):
@@ -276,6 +302,8 @@ def run(opts, wplus_steps=None, log=None):
     out_size = (opts.get('network_g') or {}).get('out_size')
     lpips_size = check_lpips_size(inv.get('lpips_size'), out_size if isinstance(out_size, int) else None, 'inversion.lpips_size')
     sched = schedule_options(inv)
+    sched.update(latent_options(inv))
+    edit_at = edit_option(inv)
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
     model = load_model(opts).cuda().eval()
@@ -295,11 +323,22 @@ def run(opts, wplus_steps=None, log=None):
         graphed = GraphedForward(model)          # model(x) replayed from a hipGraph: -6 % latency per image at batch 1
     size = model.generator.size
     check_lpips_size(lpips_size, size, 'inversion.lpips_size')
+    latent_options(inv, model.generator.n_latent)
     summary = {}
     for name, dopt in opts['datasets'].items():
         files, direction = load_files_from_path(dopt, directions_dir)
         save_dir = os.path.join(save_root, name)
-        model.delta_latent.data += direction.cuda()
+        # ``edit: final`` with a W+ loop: the direction stays out of the start latents and goes on after the fit (invert(edit=...))
+        edit_final = edit_at == 'final' and steps > 0
+        edit = None
+        if edit_final:
+            if direction.dim() > 0:
+                edit = direction.cuda().float().contiguous()
+        else:
+            if steps > 0 and bool((direction != 0).any()):
+                log.warning('inversion.wplus_steps with an editing direction and inversion.edit: start — the W+ loop fits the UNEDITED input '
+                            'starting from edited latents (it works the edit off again); inversion.edit: final applies the direction after the fit')
+            model.delta_latent.data += direction.cuda()
         times, metrics = [], None
         # ``inversion.batch`` files per call (default 1 = the reference's per-file loop, run_ood_faceGAN_inversion.py:158-182): images are
         # independent on this path, and the W+ loop of one image leaves most of the GPU idle (284 ms per image alone, 131 ms in a batch of 8)
@@ -327,7 +366,7 @@ def run(opts, wplus_steps=None, log=None):
                     if steps > 0:
                         out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
                                            loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size,
-                                           noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), **sched)[0]
+                                           noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), edit=edit, **sched)[0]
                     else:
                         out = (graphed(x) if graphed is not None else model(x))[0]
                     torch.cuda.synchronize()
@@ -340,7 +379,8 @@ def run(opts, wplus_steps=None, log=None):
             if metrics is not None:
                 collect_host_metrics(done, metrics)
         wall = (time.time() - wall0) / max(len(files), 1)
-        model.delta_latent.data -= direction.cuda()
+        if not edit_final:
+            model.delta_latent.data -= direction.cuda()
         mean = lambda v: float(np.mean(v)) if v else float('nan')
         summary[name] = dict(n=len(files), time=mean(times), wall=wall, psnr=mean((metrics or {}).get('psnr')),
                              ssim=mean((metrics or {}).get('ssim')))

@@ -807,6 +807,13 @@ class _WRun:
         # latent prior: latent_reg * mean (w - anchor)^2 per image, a fourth loss table; the anchor is constant for the run
         self.anchor = anchor
         self.lat_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.latent_reg != 0.0 else None
+        # latent controls: with any of them on, ops.latent_step takes the place of the Adam call.  The per-layer factors are a
+        # persistent device buffer like ``w_in``, for the same reason: it must never be born inside a recorded step.  ``delta_reg`` brings a
+        # fifth loss table, the squared spread of the layers about their mean per step and image
+        self.tied = inv.latent_space == 'w'
+        self.layer_lr = None if inv.layer_lr is None else torch.tensor(inv.layer_lr, dtype=torch.float32, device=self.w.device)
+        self.dl_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.delta_reg != 0.0 else None
+        self.controls = self.tied or self.layer_lr is not None or self.dl_table is not None
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
@@ -834,13 +841,18 @@ class _WRun:
         eng, inv = self.eng, self.inv
         w_in = self.w
         if self.w_in is not None:
-            w_in = ops.latent_noise(self.w, self.dev_t, self.ids, self.steps, inv.latent_noise, inv.noise_ramp, inv.noise_seed, out=self.w_in)
+            # W: one vector of noise per image, repeated over the layers — the rows of w_in stay identical
+            w_in = ops.latent_noise(self.w, self.dev_t, self.ids, self.steps, inv.latent_noise, inv.noise_ramp, inv.noise_seed, out=self.w_in,
+                                    period=self.w.shape[-1] if self.tied else None)
         img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
         gimg = self._loss_grad(img)
         g = eng.backward(gimg, self.gmul, carry_scale=True)
         if self.lat_table is not None:          # evaluated at w, not at the perturbed w_in
             ops.latent_prior_loss_grad(self.w, self.anchor, g, inv.latent_reg, table=self.lat_table, row_dev=self.dev_t)
-        if inv.lr_rampup > 0.0 or inv.lr_rampdown > 0.0:
+        if self.controls:                       # spread term, W tie, per-layer step sizes and Adam: one kernel, the launch count of the Adam call
+            ops.latent_step(self.w, g, self.m, self.v, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown, inv.lr, inv.betas, inv.eps,
+                            layer_lr=self.layer_lr, delta_reg=inv.delta_reg, tied=self.tied, table=self.dl_table)
+        elif inv.lr_rampup > 0.0 or inv.lr_rampdown > 0.0:
             ops.adam_step_dev_sched(self.w, g, self.m, self.v, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown, inv.lr, inv.betas, inv.eps)
         else:
             ops.adam_step_dev(self.w, g, self.m, self.v, self.dev_t, inv.lr, inv.betas, inv.eps)
@@ -1035,6 +1047,44 @@ def check_pixel_loss(pixel_loss, pixel_scale, name='pixel_loss', scale_name='pix
     return pixel_loss, s.item()
 
 
+LATENT_SPACES = ('w+', 'w')
+
+
+def check_latent_space(value, name='latent_space'):
+    """Where the W+ loop moves: 'w+' (default: every layer its own vector) or 'w' (one vector per image); anything else raises ValueError."""
+    if not isinstance(value, str) or value not in LATENT_SPACES:
+        raise ValueError(f'{name} must be one of {list(LATENT_SPACES)}, got {value!r}')
+    return value
+
+
+def check_layer_lr(value, n_layers=None, name='layer_lr'):
+    """The per-layer factors of the learning rate as a tuple of floats (None stays None): ValueError unless it is a list / tuple of finite real
+    numbers >= 0 (no bools, no strings) and, once the number of layers is known, of that length."""
+    if value is None:
+        return None
+    if not isinstance(value, (list, tuple)) or len(value) == 0:
+        raise ValueError(f'{name} must be None or a list of finite numbers >= 0, one per layer, got {value!r}')
+    for f in value:
+        if isinstance(f, bool) or not isinstance(f, numbers.Real) or not (math.isfinite(f) and f >= 0):
+            raise ValueError(f'{name} must hold finite numbers >= 0, got {f!r} in {list(value)!r}')
+    if n_layers is not None and len(value) != n_layers:
+        raise ValueError(f'{name} must have one entry per layer ({n_layers}), got {len(value)}')
+    return tuple(float(f) for f in value)
+
+
+def check_latent_controls(latent_space, layer_lr, delta_reg, n_layers=None, prefix=''):
+    """(latent_space, layer_lr, delta_reg) checked one by one and together: in W there is one vector per image, so per-layer rates mean
+    nothing and the spread of the layers is identically zero — both raise ValueError there."""
+    space = check_latent_space(latent_space, prefix + 'latent_space')
+    rates = check_layer_lr(layer_lr, n_layers, prefix + 'layer_lr')
+    reg = check_nonneg(delta_reg, prefix + 'delta_reg')
+    if space == 'w' and rates is not None:
+        raise ValueError(f"{prefix}layer_lr with {prefix}latent_space 'w': there is only one vector per image")
+    if space == 'w' and reg != 0.0:
+        raise ValueError(f"{prefix}delta_reg with {prefix}latent_space 'w': the layers are identical there, the term is zero")
+    return space, rates, reg
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1059,13 +1109,19 @@ class WPlusInverter:
     max(0, 1 - (t / steps) / noise_ramp)^2 (``noise_ramp`` <= 0: constant), a function of (``noise_seed``, the image's id, step, element);
     ``latent_reg``: adds latent_reg * mean (w - latent_anchor)^2 per image, evaluated at the unperturbed w (``last_terms['latent']``).
 
+    Latent controls, off by default as well.  ``latent_space='w'``: one 512-vector per image — the latent stays (B,L,512) with
+    identical rows, started at the layer mean of ``w0``; every layer receives the sum over the layers of the gradient and the latent noise is
+    one vector repeated.  ``layer_lr``: L finite factors >= 0 of ``lr``, one per layer (of the step size: Adam does not see a gradient's scale);
+    0 freezes a layer.  ``delta_reg``: adds delta_reg * mean_le (w_le - mean_l w_le)^2 per image, the squared spread of the layers about their
+    mean, at the unperturbed w (``last_terms['delta']``); W is its limit.  'w' with either of the other two raises ValueError.
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
-                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None):
+                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
         # the size the LPIPS term is taken at (DESIGN.md §14): None = the image's own, today's path; an int: the image and the target are
         # area-pooled to it first (the projectors' value is 256).  The image size is known in ``invert``: the part of the check that needs it runs there
@@ -1076,7 +1132,7 @@ class WPlusInverter:
         self.pixel_loss, self.pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
         # loss = per-image MSE + lpips_weight * LPIPS(alex) (north_star: "W+ Adam steps against LPIPS/L2"); ``lpips``: an oodgan.lpips.LPIPSAlex
         # (min_max = the generator's output range).  Off by default: the `lpips` weights are third-party and absent here (parity unpinned).
-        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'pixel', 'mse', 'lpips', 'ssim', 'latent'} tables (None: term off;
+        # ``invert`` then returns the TOTAL loss per step and image; ``last_terms`` = {'pixel', 'mse', 'lpips', 'ssim', 'latent', 'delta'} tables (None: term off;
         # 'pixel' is the pixel term's table whatever its kind, 'mse' the same tensor when ``pixel_loss`` is 'mse' and None otherwise).
         self.lpips, self.lpips_weight = lpips, float(lpips_weight)
         # + ssim_weight * (1 - SSIM): the metric the CLI reports, on the unrounded images; 0 (default) = the term, its
@@ -1085,6 +1141,8 @@ class WPlusInverter:
         self.lr_rampup, self.lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         self.latent_noise, self.noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
         self.noise_seed, self.latent_reg = check_noise_seed(noise_seed), check_nonneg(latent_reg, 'latent_reg')
+        # latent controls, all off by default: the step is then the launch list above.  The number of layers is known in ``invert``
+        self.latent_space, self.layer_lr, self.delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg)
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
@@ -1112,6 +1170,9 @@ class WPlusInverter:
         size = check_lpips_size(self.lpips_size, int(target.shape[-1]))
         self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
         ids, anchor = self._sched_inputs(w0, noise_ids, latent_anchor)
+        check_layer_lr(self.layer_lr, int(w0.shape[1]))
+        if self.latent_space == 'w':            # the start: the layer mean, on every layer (set-up, not the step)
+            w0 = w0.detach().mean(dim=1, keepdim=True).expand_as(w0).contiguous()
         if loss_weight is not None:
             if tuple(loss_weight.shape) != (B, 1) + tuple(target.shape[2:]) or loss_weight.dtype != torch.float32 or loss_weight.device != target.device:
                 raise ValueError(f'loss_weight must be a float32 {(B, 1) + tuple(target.shape[2:])} tensor on {target.device}, got '
@@ -1148,7 +1209,10 @@ class WPlusInverter:
                          (self.ssim_weight != 0.0, 'the SSIM term'),
                          (self.pixel_loss != 'mse', 'a robust pixel term'),
                          (self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0,
-                          'the projector schedule (lr ramps, latent noise, latent prior)')):
+                          'the projector schedule (lr ramps, latent noise, latent prior)'),
+                         (self.latent_space != 'w+', "latent_space 'w'"),
+                         (self.layer_lr is not None, 'layer_lr'),
+                         (self.delta_reg != 0.0, 'delta_reg')):
             if on:
                 raise NotImplementedError(f'use_graph with {what}: use the launch plans (default) instead')
 
@@ -1236,15 +1300,16 @@ class WPlusInverter:
         self.last_stats = {'steps_run': [r.steps_run for r in runs], 'rollbacks': [r.rollbacks for r in runs]}
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
-                                                             [r.lat_table for r in runs]])
+                                                             [r.lat_table for r in runs], [r.dl_table for r in runs]])
         # a graph run has no per-window guard: its flags are read once, here, and a flagged inversion is repeated through the guarded loop
         if use_graph and any(eng.bwd_scale_violated() or eng.fwd_range_violated() for eng in engines):
             return self.invert(target, w0, noises, steps, streams=streams, use_graph=False)
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None):
-        self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat}
+    def _total(self, mse, lp, ss=None, lat=None, dl=None):
+        self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
-        return total if lat is None else total + self.latent_reg * lat
+        total = total if lat is None else total + self.latent_reg * lat
+        return total if dl is None else total + self.delta_reg * dl

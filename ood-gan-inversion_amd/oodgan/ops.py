@@ -1460,11 +1460,13 @@ def adam_step_dev_sched(w, g, m, v, t_dev, total_steps, rampup, rampdown, lr=0.0
     return w
 
 
-def latent_noise(w, t_dev, ids, total_steps, sigma0, noise_ramp=0.75, seed=0, out=None):
+def latent_noise(w, t_dev, ids, total_steps, sigma0, noise_ramp=0.75, seed=0, out=None, period=None):
     """w_in = w + sigma_i * n(seed, ids[b], i, e) (oodgan_latent_noise): w (B, ...) float32, i = t_dev[0] (int32[1] on the device, not
     changed), ids int64 (B,) on the device, sigma_i = sigma0 * max(0, 1 - (i / total_steps) / noise_ramp)^2 (noise_ramp <= 0: sigma0).  The
     draws are a pure function of (seed, id, step, element) — tests/latent_noise_ref.py restates them in float64.  ``out``: the buffer
-    that receives w_in (the W+ loop's persistent one); returns it."""
+    that receives w_in (the W+ loop's persistent one); returns it.  ``period`` (oodgan_latent_noise_tied): element e of an image takes the draw
+    of element e mod period — the W mode's one 512-vector of noise for all layers; a multiple of 4 that divides the image's element count, or
+    ValueError.  None: every element its own draw."""
     a = _dev(w, 'w')
     B = a.shape[0]
     if out is None:
@@ -1473,8 +1475,15 @@ def latent_noise(w, t_dev, ids, total_steps, sigma0, noise_ramp=0.75, seed=0, ou
     assert ids.shape == (B,) and ids.dtype == torch.int64 and ids.is_contiguous() and ids.device == a.device, \
         'latent_noise: ids must be a contiguous int64 (B,) tensor on the latent\'s device'
     assert t_dev.dtype == torch.int32 and t_dev.device == a.device
-    check(_lib.lib().oodgan_latent_noise(_p(a), _p(out), _p(ids), _p(t_dev), B, a.numel() // B, int(seed), int(total_steps), float(sigma0),
-                                         float(noise_ramp), _stream()), 'latent_noise')
+    n = a.numel() // B
+    if period is None:
+        check(_lib.lib().oodgan_latent_noise(_p(a), _p(out), _p(ids), _p(t_dev), B, n, int(seed), int(total_steps), float(sigma0),
+                                             float(noise_ramp), _stream()), 'latent_noise')
+        return out
+    if isinstance(period, bool) or not isinstance(period, int) or period <= 0 or period % 4 != 0 or n % period != 0:
+        raise ValueError(f'latent_noise: period must be a multiple of 4 that divides the {n} elements of an image, got {period!r}')
+    check(_lib.lib().oodgan_latent_noise_tied(_p(a), _p(out), _p(ids), _p(t_dev), B, n, period, int(seed), int(total_steps), float(sigma0),
+                                              float(noise_ramp), _stream()), 'latent_noise_tied')
     return out
 
 
@@ -1499,3 +1508,36 @@ def latent_prior_loss_grad(w, anchor, g=None, weight=1.0, loss_out=None, table=N
     else:
         check(L.oodgan_latent_prior_fwd_bwd(_p(a), _p(c), _p(g), _p(dst), B, n, batched, float(weight), _stream()), 'latent_prior')
     return loss
+
+
+# ---- latent controls of the W+ loop (csrc/wplus_sched.hip)
+def latent_step(w, g, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.01, betas=(0.9, 0.999), eps=1e-8, layer_lr=None, delta_reg=0.0,
+                tied=False, table=None, loss_out=None):
+    """``adam_step_dev_sched`` with the latent controls (oodgan_latent_step) on w, g, m, v (B, L, D), all contiguous float32 and updated in
+    place.  ``delta_reg`` = lambda: g += lambda * dR/dw for R_b = mean_le (w_le - mean_l w_le)^2, the squared spread of the layers about
+    their mean; ``tied``: every layer receives the sum over the layers of g (the gradient of one vector per image); ``layer_lr``: float32 (L,)
+    on the device, a factor of the step size per layer (0 freezes the layer).  g holds afterwards what Adam consumed.  R goes to row
+    t_dev[0] (before the increment, clamped) of ``table`` (nrows, B), or to ``loss_out`` (B,); with neither it is not written.  Nothing on:
+    the bits of ``adam_step_dev_sched``.  Returns w."""
+    a = _dev(w, 'w')
+    if a.dim() != 3:
+        raise ValueError(f'latent_step: w must be (B, L, D), got {tuple(a.shape)}')
+    B, L, D = a.shape
+    for t, name in ((w, 'w'), (g, 'g'), (m, 'm'), (v, 'v')):
+        assert isinstance(t, torch.Tensor) and t.shape == a.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == a.device, \
+            f'latent_step: {name} must be a contiguous float32 tensor of the latent\'s shape on its device (it is updated in place)'
+    assert t_dev.dtype == torch.int32 and t_dev.device == a.device
+    if layer_lr is not None:
+        assert layer_lr.shape == (L,) and layer_lr.dtype == torch.float32 and layer_lr.is_contiguous() and layer_lr.device == a.device, \
+            f'latent_step: layer_lr must be a contiguous float32 ({L},) tensor on the latent\'s device'
+    dst, nrows = None, 0
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and table.device == a.device
+        dst, nrows = table, table.shape[0]
+    elif loss_out is not None:
+        assert loss_out.shape == (B,) and loss_out.dtype == torch.float32 and loss_out.is_contiguous() and loss_out.device == a.device
+        dst, nrows = loss_out, 1
+    check(_lib.lib().oodgan_latent_step(_p(w), _p(g), _p(m), _p(v), B, L, D, float(lr), float(betas[0]), float(betas[1]), float(eps), _p(t_dev),
+                                        int(total_steps), float(rampup), float(rampdown), _p(layer_lr), float(delta_reg), int(bool(tied)),
+                                        _p(dst), nrows, _stream()), 'latent_step')
+    return w
