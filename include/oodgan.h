@@ -130,6 +130,11 @@ int oodgan_blur_bias_act(const float* x, const float* kernel, float* y, int B, i
  * per generator forward.  latent (B,L,S); wcat (R,S); bcat (R) or NULL; row_lat int32 (R) or NULL (all 0). */
 int oodgan_style_affine_fwd(const float* latent, const float* wcat, const float* bcat, const int* row_lat,
                             float* s, int B, int L, int S, int R, float scale, float lr_mul, void* stream);
+/* StyleSpace offsets: oodgan_style_affine_fwd with offset (B,R) added to its result,
+ * s[b,r] = (the value oodgan_style_affine_fwd writes) + offset[b,r]: one more fp32 addition after the affine's own rounding, on both
+ * routes (matrix cores and one wave per row).  offset all zeros: the output compares equal to oodgan_style_affine_fwd's. */
+int oodgan_style_affine_fwd_offset(const float* latent, const float* wcat, const float* bcat, const int* row_lat, const float* offset,
+                                   float* s, int B, int L, int S, int R, float scale, float lr_mul, void* stream);
 /* The MFMA path (R%16==0 and S%16==0) requires every aligned group of 16 rows to share one latent
  * index (row_lat[r] == row_lat[r & ~15]); the generator's channel counts guarantee it.
  * glat[b,l,k] = scale * sum_{r in [lat_start[l], lat_start[l+1])} gs[b,r]*wcat[r,k]  (overwrites glat);
@@ -706,6 +711,22 @@ int oodgan_latent_noise_tied(const float* w, float* w_in, const long* ids, const
 int oodgan_latent_step(float* w, float* g, float* m, float* v, int B, int L, int D, float lr, float beta1, float beta2, float eps,
                        int* t_dev, int total_steps, float rampup, float rampdown, const float* layer_lr, float delta_reg, int tied,
                        float* delta_table, int nrows, void* stream);
+/* StyleSpace step: the loop's state is an offset delta (B, R) on the styles, s = style_affine(w0) + delta, and gs (B, R) is
+ * dL/ds as the backward pass leaves it, times the loss scale grad_div.  Takes the place of the Adam call like oodgan_latent_step.
+ * Increments t_dev[0] first (t), then per image, one block each:
+ *   g_r = gs_r / grad_div (a correctly rounded division);
+ *   R_b = mean_r delta_r^2 (double sum, rounded once), written to row min(t - 1, nrows - 1) of reg_table (nrows, B); reg_table NULL: not written;
+ *   style_reg > 0: g_r += 2 style_reg / R * delta_r (the gradient of style_reg * R_b);
+ *   g is written back to gs: it holds what Adam consumed;
+ *   Adam as oodgan_adam_step_dev_sched with the step size (float)((double)lr * (double)layer_lr[row_lat[r]] * r(t - 1) / (1 - beta1^t));
+ *   row_lat int32 (R): the latent each style row reads; layer_lr (floats on the device, one per latent named by row_lat) NULL: no factor,
+ *   and row_lat is not read; layer_lr without row_lat is refused (-1).  A factor 0 leaves those rows of delta bit-unchanged (their moments still move).
+ * No atomics: bit-reproducible.  grad_div 1, layer_lr NULL, style_reg 0 and reg_table NULL: delta, m, v, t bit-identical to
+ * oodgan_adam_step_dev_sched on the same flat buffers.  style_reg * R_b pulls the fit towards styles some w can produce; like delta_reg it
+ * is this build's own term (StyleSpace: Wu et al., CVPR 2021, defines the space, not a regulariser). */
+int oodgan_style_step(float* delta, float* gs, float* m, float* v, int B, int R, float lr, float beta1, float beta2, float eps, int* t_dev,
+                      int total_steps, float rampup, float rampdown, float grad_div, const int* row_lat, const float* layer_lr,
+                      float style_reg, float* reg_table, int nrows, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

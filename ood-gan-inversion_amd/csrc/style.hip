@@ -9,7 +9,10 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// s[b, r] = scale * sum_k W[r,k] * lat[b, row_lat[r], k] + bias[r]*lr_mul
+// StyleSpace offset: the style as the affine rounds it, then + offset[b,r] as one more fp32 addition; NULL: the style itself
+__device__ __forceinline__ float add_offset(float v, const float* __restrict__ offset, long i) { return offset ? v + offset[i] : v; }
+
+// s[b, r] = scale * sum_k W[r,k] * lat[b, row_lat[r], k] + bias[r]*lr_mul  (+ offset[b, r])
 // MFMA path: one wave per 16-row tile x 16 batch columns; v_mfma_f32_16x16x4_f32:
 //   A[i=l&15][k=l>>4] = W[r0+i][k], B[k=l>>4][j=l&15] = lat[b0+j][.][k]; each lane loads 16 B of both
 //   operands per 16-deep K step and issues 4 MFMAs (k order inside a step is irrelevant for a sum as long
@@ -19,7 +22,7 @@ namespace {
 __global__ __launch_bounds__(256) void style_affine_mfma_kernel(const float* __restrict__ lat, const float* __restrict__ w,
                                                                 const float* __restrict__ bias, const int* __restrict__ row_lat,
                                                                 float* __restrict__ s, int B, int L, int S, int R, float scale,
-                                                                float lr_mul) {
+                                                                float lr_mul, const float* __restrict__ offset) {
     const int lane = threadIdx.x & 63;
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int r0 = tile * 16;
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(256) void style_affine_mfma_kernel(const float* __r
                 float acc = 0.f;
                 for (int k = lane; k < S; k += 64) acc += w[r * S + k] * lp[k];
                 acc = wave_sum(acc);
-                if (lane == 0) s[(long)b * R + r] = acc * scale + bv;
+                if (lane == 0) s[(long)b * R + r] = add_offset(acc * scale + bv, offset, (long)b * R + r);
             }
         }
         return;
@@ -61,7 +64,7 @@ __global__ __launch_bounds__(256) void style_affine_mfma_kernel(const float* __r
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int r = r0 + kq * 4 + q;
-            s[(long)bj * R + r] = acc[q] * scale + (bias ? bias[r] * lr_mul : 0.f);
+            s[(long)bj * R + r] = add_offset(acc[q] * scale + (bias ? bias[r] * lr_mul : 0.f), offset, (long)bj * R + r);
         }
     }
 }
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void style_affine_mfma_kernel(const float* __r
 __global__ __launch_bounds__(256) void style_affine_wave_kernel(const float* __restrict__ lat, const float* __restrict__ w,
                                                                 const float* __restrict__ bias, const int* __restrict__ row_lat,
                                                                 float* __restrict__ s, int B, int L, int S, int R, float scale,
-                                                                float lr_mul) {
+                                                                float lr_mul, const float* __restrict__ offset) {
     const int lane = threadIdx.x & 63;
     const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (r >= R) return;
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(256) void style_affine_wave_kernel(const float* __r
         float acc = 0.f;
         for (int k = lane; k < S; k += 64) acc += w[r * S + k] * lp[k];
         acc = wave_sum(acc);
-        if (lane == 0) s[(long)b * R + r] = acc * scale + bv;
+        if (lane == 0) s[(long)b * R + r] = add_offset(acc * scale + bv, offset, (long)b * R + r);
     }
 }
 
@@ -233,18 +236,31 @@ __global__ __launch_bounds__(256) void demod_bwd_kernel(const float* __restrict_
 
 }  // namespace
 
-extern "C" int oodgan_style_affine_fwd(const float* latent, const float* wcat, const float* bcat, const int* row_lat, float* s,
-                                       int B, int L, int S, int R, float scale, float lr_mul, void* stream) {
-    OODGAN_REQUIRE(latent && wcat && s && B > 0 && L > 0 && S > 0 && R > 0, "style_affine_fwd: bad args");
+namespace {
+int style_affine_fwd(const float* latent, const float* wcat, const float* bcat, const int* row_lat, const float* offset, float* s, int B, int L,
+                     int S, int R, float scale, float lr_mul, void* stream, const char* what) {
     hipStream_t st = as_stream(stream);
     const bool mfma = (R % 16 == 0) && (S % 16 == 0);
     if (mfma)
         hipLaunchKernelGGL(style_affine_mfma_kernel, dim3((R / 16 + 3) / 4, (B + 15) / 16), dim3(256), 0, st, latent, wcat, bcat,
-                           row_lat, s, B, L, S, R, scale, lr_mul);
+                           row_lat, s, B, L, S, R, scale, lr_mul, offset);
     else
         hipLaunchKernelGGL(style_affine_wave_kernel, dim3((R + 3) / 4), dim3(256), 0, st, latent, wcat, bcat, row_lat, s, B, L,
-                           S, R, scale, lr_mul);
-    return check_launch("style_affine_fwd");
+                           S, R, scale, lr_mul, offset);
+    return check_launch(what);
+}
+}  // namespace
+
+extern "C" int oodgan_style_affine_fwd(const float* latent, const float* wcat, const float* bcat, const int* row_lat, float* s,
+                                       int B, int L, int S, int R, float scale, float lr_mul, void* stream) {
+    OODGAN_REQUIRE(latent && wcat && s && B > 0 && L > 0 && S > 0 && R > 0, "style_affine_fwd: bad args");
+    return style_affine_fwd(latent, wcat, bcat, row_lat, nullptr, s, B, L, S, R, scale, lr_mul, stream, "style_affine_fwd");
+}
+
+extern "C" int oodgan_style_affine_fwd_offset(const float* latent, const float* wcat, const float* bcat, const int* row_lat, const float* offset,
+                                              float* s, int B, int L, int S, int R, float scale, float lr_mul, void* stream) {
+    OODGAN_REQUIRE(latent && wcat && offset && s && B > 0 && L > 0 && S > 0 && R > 0, "style_affine_fwd_offset: bad args");
+    return style_affine_fwd(latent, wcat, bcat, row_lat, offset, s, B, L, S, R, scale, lr_mul, stream, "style_affine_fwd_offset");
 }
 
 extern "C" int oodgan_style_affine_bwd(const float* gs, const float* wcat, const int* lat_start, float* glat, int B, int L,

@@ -214,6 +214,49 @@ __global__ __launch_bounds__(256) void latent_step_kernel(float* __restrict__ w,
     if (threadIdx.x == 0) table[loss_row(&row, nrows, gridDim.x) + blockIdx.x] = (float)(((red[0] + red[1]) + (red[2] + red[3])) * inv_n);
 }
 
+// ---------------------------------------------------------------------------------------------------------------- style step
+// The StyleSpace side of a step: the loop optimises an offset d (B, R) on the styles, gs is dL/ds as the backward pass left it
+// (times the loss scale).  grid: (B), one block per image; a thread owns the columns r = tid, tid + 256, ...: every access is coalesced.
+//   g_r = gs_r / grad_div (a correctly rounded division; grad_div == 1: gs_r);  R_b = mean_r d_r^2 (double sum, one rounding) -> table row t - 1;
+//   coef != 0: g_r += coef * d_r;  g is written back: gs holds what Adam consumed;
+//   Adam: the expressions of adam_dev_sched_kernel with lr * layer_lr[row_lat[r]].
+// grad_div 1, no factors, coef 0: the bits of adam_dev_sched_kernel.
+__global__ __launch_bounds__(256) void style_step_kernel(float* __restrict__ w, float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                         int R, float lr, float beta1, float beta2, float eps, const int* __restrict__ t_dev,
+                                                         int total_steps, float rampup, float rampdown, float grad_div,
+                                                         const int* __restrict__ row_lat, const float* __restrict__ layer_lr, float coef,
+                                                         float* __restrict__ table, int nrows, double inv_n) {
+    __shared__ double red[4];
+    const int t = t_dev[0];
+    const double bc1 = 1.0 - pow((double)beta1, (double)t), bc2 = 1.0 - pow((double)beta2, (double)t);
+    const double mult = lr_multiplier(t - 1, total_steps, rampup, rampdown);
+    const float step_all = (float)((double)lr * mult / bc1);
+    const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
+    const long base = (long)blockIdx.x * R;
+    double acc = 0.0;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        const long i = base + r;
+        const float d = w[i];
+        acc += (double)d * (double)d;
+        float gi = g[i] / grad_div;
+        if (coef != 0.f) gi += coef * d;
+        g[i] = gi;
+        const float step_size = layer_lr ? (float)((double)lr * (double)layer_lr[row_lat[r]] * mult / bc1) : step_all;
+        const float mi = m[i] + (gi - m[i]) * (1.f - beta1);
+        const float vi = v[i] * beta2 + (1.f - beta2) * gi * gi;
+        m[i] = mi;
+        v[i] = vi;
+        w[i] = d - step_size * (mi / (sqrtf(vi) * inv_bc2_sqrt + eps));
+    }
+    if (table == nullptr) return;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    const int row = t - 1;
+    if (threadIdx.x == 0) table[loss_row(&row, nrows, gridDim.x) + blockIdx.x] = (float)(((red[0] + red[1]) + (red[2] + red[3])) * inv_n);
+}
+
 }  // namespace
 
 extern "C" int oodgan_adam_step_dev_sched(float* w, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
@@ -261,4 +304,19 @@ extern "C" int oodgan_latent_step(float* w, float* g, float* m, float* v, int B,
     hipLaunchKernelGGL(latent_step_kernel, dim3(B), dim3(256), 0, as_stream(stream), w, g, m, v, L, D, lr, beta1, beta2, eps, t_dev, total_steps,
                        rampup, rampdown, layer_lr, (float)(2.0 * (double)delta_reg / n), tied, delta_table, nrows, 1.0 / n);
     return check_launch("latent_step");
+}
+
+extern "C" int oodgan_style_step(float* delta, float* gs, float* m, float* v, int B, int R, float lr, float beta1, float beta2, float eps,
+                                 int* t_dev, int total_steps, float rampup, float rampdown, float grad_div, const int* row_lat,
+                                 const float* layer_lr, float style_reg, float* reg_table, int nrows, void* stream) {
+    OODGAN_REQUIRE(delta && gs && m && v && t_dev && B > 0 && R > 0 && total_steps > 0, "style_step: bad args");
+    OODGAN_REQUIRE(B <= 65535 * 1024, "style_step: B = %d: too large", B);
+    OODGAN_REQUIRE(layer_lr == nullptr || row_lat != nullptr, "style_step: layer_lr without row_lat");
+    OODGAN_REQUIRE(grad_div > 0.f && style_reg >= 0.f && (reg_table == nullptr || nrows > 0), "style_step: grad_div = %g, style_reg = %g, nrows = %d",
+                   (double)grad_div, (double)style_reg, nrows);
+    hipLaunchKernelGGL(sched_counter_inc_kernel, dim3(1), dim3(1), 0, as_stream(stream), t_dev);
+    hipLaunchKernelGGL(style_step_kernel, dim3(B), dim3(256), 0, as_stream(stream), delta, gs, m, v, R, lr, beta1, beta2, eps, t_dev, total_steps,
+                       rampup, rampdown, grad_div, row_lat, layer_lr, (float)(2.0 * (double)style_reg / (double)R), reg_table, nrows,
+                       1.0 / (double)R);
+    return check_launch("style_step");
 }

@@ -72,6 +72,7 @@ _SIGS = {
     'oodgan_upfirdn2d': (c_int, [P, P, P] + [c_int] * 15 + [P]),
     'oodgan_blur_bias_act': (c_int, [P, P, P] + [c_int] * 9 + [P, P, c_int, P, c_int, P]),
     'oodgan_style_affine_fwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P]),
+    'oodgan_style_affine_fwd_offset': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P]),
     'oodgan_style_affine_bwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, P]),
     'oodgan_equal_linear': (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_int, P]),
     'oodgan_equal_linear_grouped': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, P]),
@@ -183,6 +184,8 @@ _SIGS = {
     'oodgan_latent_noise_tied': (c_int, [P, P, P, P, c_int, c_long, c_long, c_long, c_int, c_float, c_float, P]),
     'oodgan_latent_step': (c_int, [P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, P, c_float,
                                    c_int, P, c_int, P]),
+    'oodgan_style_step': (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, c_float, P, P, c_float,
+                                  P, c_int, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
     'oodgan_u8_to_input': (c_int, [P, P, P, c_int, c_int, c_int, P]),

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
 from .modules import Generator
 from .synth import generator_channels
 
@@ -215,18 +215,19 @@ class ood_faceGAN_e4e(nn.Module):
         """generate() of the reference (e4e :268-313 / restyle :246-283): feats_conv -> hooked generator -> mask blend."""
         self.ori_lats = lats
         noise = kwargs.get('noise', None)
+        offs = kwargs.get('style_offsets', None)        # StyleSpace offsets (B, R) on the generator's styles (DESIGN.md §19); the hooks read ``lats``
         if self.modulation is None:
-            out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise)
+            out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs)
             return out, lats
-        out = self._hooked_generate(lats, enc_feats, noise)
+        out = self._hooked_generate(lats, enc_feats, noise, offs)
         if self.blend_with_gen:
             if self.skip_SA:
-                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise)
+                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs)
             for _ in range(self.blend_cnt):
                 out = self.blend(x, out, alpha_scale=None)
         return out, lats
 
-    def _hooked_generate(self, lats, enc_feats, noise):
+    def _hooked_generate(self, lats, enc_feats, noise, style_offsets=None):
         """The generator pass with the SAMM hooks (e4e :268-297): fills ``self.aligns`` with the per-level fields; returns G's image."""
         self.feats = [samm.conv1x1(enc_feats[i], self.feats_conv[i].weight, self.feats_conv[i].bias) for i in range(4)]
         self.lats = lats
@@ -235,7 +236,7 @@ class ood_faceGAN_e4e(nn.Module):
         cond_ind = [(2 * (k + 2)) + 1 for k in range(len(conditions))]
         out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, conditions=conditions,
                                 cond_layers=cond_ind, cond_type=self.modulation_type, cond_hook=self._cond_hook,
-                                noise=noise)
+                                noise=noise, style_offsets=style_offsets)
         return out
 
     def blending_mask(self):
@@ -264,7 +265,7 @@ class ood_faceGAN_e4e(nn.Module):
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
-               delta_reg=0.0, **kwargs):
+               delta_reg=0.0, style_reg=0.0, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -319,7 +320,17 @@ class ood_faceGAN_e4e(nn.Module):
         (w_le - mean_l w_le)^2 per image, the squared spread of the layers about their mean — the symmetric, build-defined form (e4e's own
         regulariser measures the distance from layer 0); W is its lambda -> infinity limit.  ``last_loss_terms['delta']`` is its table (None
         when off).  'w' together with ``layer_lr`` or ``delta_reg``, a wrong length, a negative or a non-finite entry raise ValueError;
-        ``use_graph`` with any of the three NotImplementedError."""
+        ``use_graph`` with any of the three NotImplementedError.
+        StyleSpace (Wu et al., CVPR 2021): ``latent_space='s'`` keeps the latents at their start w0 and fits an offset delta
+        (B, R) on the per-channel styles the modulated convs consume, s = A(w0) + delta, from 0 — the space with the lowest reconstruction
+        error of Z / W / W+ / S, and the one single-channel edits live in; ``generator.style_layout()`` names the columns.  The returned
+        ``lats`` (and ``self.last_refined_lats``) are w0, ``self.last_style_offsets`` is delta (None for the other spaces), and
+        ``model(x, lats=lats, style_offsets=self.last_style_offsets)`` reproduces the output; the SAMM hooks keep reading w0.  ``style_reg`` =
+        lambda >= 0 adds lambda * mean_r delta_r^2 per image, a build-defined pull towards styles some w can produce
+        (``last_loss_terms['style']``, None when off).  ``edit`` is then a StyleSpace direction, float32 (R,), (1,R) or (B,R), added to delta for
+        the final forward only.  ``layer_lr`` scales the step of each layer's style rows.  's' with delta_reg, latent_noise or latent_reg,
+        ``style_reg`` without 's', or a W+-shaped edit in 's' raise ValueError; ``use_graph`` with 's' and a zero-padded (narrow) generator
+        NotImplementedError."""
         ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
         lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
@@ -329,9 +340,11 @@ class ood_faceGAN_e4e(nn.Module):
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         latent_space, layer_lr, delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg, self.generator.n_latent)
+        style_reg = check_style_space(latent_space, style_reg, delta_reg, latent_noise, latent_reg)
+        sspace = latent_space == 's'
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
-        edit = self._check_edit(edit, lats0)
+        edit = self._check_style_edit(edit, B, self.generator.engine().R, lats0.device) if sspace else self._check_edit(edit, lats0)
         if noise is None:
             noise = [n.expand(B, -1, -1, -1).contiguous() for n in self.generator.make_noise()]
         beta = self._loss_weight(loss_region, x, lats0, enc_feats, noise)
@@ -357,13 +370,17 @@ class ood_faceGAN_e4e(nn.Module):
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
-                            delta_reg=delta_reg)
+                            delta_reg=delta_reg, style_reg=style_reg)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
                                latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
-        kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise')}
-        self.last_refined_lats = w
-        out, lats = self._ood_forward(x, w if edit is None else (w + edit).contiguous(), enc_feats, noise=noise, **kw)
+        kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets')}
+        if sspace:          # w is the offset on the styles; the latents are the start's
+            self.last_refined_lats, self.last_style_offsets = lats0, w
+            out, lats = self._ood_forward(x, lats0, enc_feats, noise=noise, style_offsets=w if edit is None else (w + edit).contiguous(), **kw)
+        else:
+            self.last_refined_lats, self.last_style_offsets = w, None
+            out, lats = self._ood_forward(x, w if edit is None else (w + edit).contiguous(), enc_feats, noise=noise, **kw)
         # An inversion returns finished results.  Without this the host runs ahead into the next inversion's set-up while the device still works
         # on this one: blocks this inversion's side streams freed are then not yet reusable, the caching allocator goes to the driver for new ones
         # and every inversion pays ~20 ms (measured, bench.py back-to-back inversions on one box: 1054-1061 ms without, 1036-1047 ms with it —
@@ -382,6 +399,17 @@ class ood_faceGAN_e4e(nn.Module):
                 or edit.device != lats0.device):
             got = f'{edit.dtype} {tuple(edit.shape)} on {edit.device}' if isinstance(edit, torch.Tensor) else repr(edit)
             raise ValueError(f'edit must be a float32 {(L, D)}, {(1, L, D)} or {(B, L, D)} tensor on {lats0.device}, got {got}')
+        return edit.detach()
+
+    @staticmethod
+    def _check_style_edit(edit, B, R, device):
+        """``invert(latent_space='s', edit=...)``: None, or a float32 (R,) / (1,R) / (B,R) StyleSpace direction on the device (ValueError otherwise)."""
+        if edit is None:
+            return None
+        if (not isinstance(edit, torch.Tensor) or tuple(edit.shape) not in ((R,), (1, R), (B, R)) or edit.dtype != torch.float32
+                or edit.device != device):
+            got = f'{edit.dtype} {tuple(edit.shape)} on {edit.device}' if isinstance(edit, torch.Tensor) else repr(edit)
+            raise ValueError(f"edit with latent_space 's' must be a float32 {(R,)}, {(1, R)} or {(B, R)} StyleSpace direction on {device}, got {got}")
         return edit.detach()
 
     def _loss_weight(self, loss_region, x, lats0, enc_feats, noise):

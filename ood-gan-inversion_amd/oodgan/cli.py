@@ -46,7 +46,10 @@ Edits and the latent controls of the W+ loop, in the same block
                                  works the edit off again (logged once as a warning).  final: the loop runs on the unedited latents and the
                                  direction is added to the refined latents for the final forward (``invert(edit=...)``).  Without W+ steps both
                                  are the reference's ``delta_latent += direction``.
-    latent_space: w+ | w         w+ (default): every layer its own vector.  w: one 512-vector per image, started at the layer mean.
+    latent_space: w+ | w | s     w+ (default): every layer its own vector.  w: one 512-vector per image, started at the layer mean.  s: StyleSpace
+                                  — the latents stay at their start and an offset on the per-channel styles is fitted; not with
+                                 ``delta_reg``, ``latent_noise``, ``latent_reg``, nor with ``edit: final`` and a data set's (W+) editing direction.
+    style_reg: <lambda>          ``latent_space: s`` only: adds lambda * the mean squared style offset per image.  Default 0 = off.
     layer_lr: [f, ...]           one factor >= 0 of ``lr`` per generator layer (18 at 1024²); 0 freezes a layer.  Not with ``latent_space: w``.
     delta_reg: <lambda>          adds lambda * the squared spread of the layers about their mean per image (the symmetric form of e4e's
                                  regulariser, which measures from layer 0).  Default 0 = off.  Not with ``latent_space: w``.
@@ -74,7 +77,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -165,6 +168,22 @@ def latent_options(inv, n_layers=None):
     generator's layer count once the model exists."""
     space, rates, reg = check_latent_controls(inv.get('latent_space', 'w+'), inv.get('layer_lr'), inv.get('delta_reg', 0.0), n_layers, 'inversion.')
     return dict(latent_space=space, layer_lr=None if rates is None else list(rates), delta_reg=reg)
+
+
+def style_options(inv):
+    """``inversion.style_reg`` for ``model.invert``, checked against ``inversion.latent_space`` and the options StyleSpace excludes (ValueError
+    names the option)."""
+    return dict(style_reg=check_style_space(inv.get('latent_space', 'w+'), inv.get('style_reg', 0.0), inv.get('delta_reg', 0.0),
+                                            inv.get('latent_noise', 0.0), inv.get('latent_reg', 0.0), 'inversion.'))
+
+
+def check_edit_space(edit_at, latent_space, has_direction, name=''):
+    """``edit: final`` hands the data set's direction to ``invert(edit=)``; with ``latent_space: s`` that must be a StyleSpace direction, and
+    the direction files of the reference are W+ (there is no S-direction file format): ValueError."""
+    if edit_at == 'final' and latent_space == 's' and has_direction:
+        raise ValueError(f"inversion.edit: final with inversion.latent_space: s: the editing direction of data set {name!r} is a W+ direction, "
+                         "the fit runs in StyleSpace and takes StyleSpace directions only (there is no file format for those); use "
+                         "inversion.edit: start, or latent_space: w+")
 
 
 def edit_option(inv):
@@ -303,13 +322,17 @@ def run(opts, wplus_steps=None, log=None):
     lpips_size = check_lpips_size(inv.get('lpips_size'), out_size if isinstance(out_size, int) else None, 'inversion.lpips_size')
     sched = schedule_options(inv)
     sched.update(latent_options(inv))
+    sched.update(style_options(inv))
     edit_at = edit_option(inv)
+    steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
+    directions_dir = opts.get('directions_dir', './directions')
+    if edit_at == 'final' and steps > 0 and sched['latent_space'] == 's':      # before the model is built and any data set is processed
+        for name, dopt in opts['datasets'].items():
+            check_edit_space(edit_at, 's', load_direction(directions_dir, dopt.get('editing')).dim() > 0, name)
     if not torch.cuda.is_available():
         raise RuntimeError('oodgan.cli needs a ROCm GPU: the HIP path has no CPU fallback')
     model = load_model(opts).cuda().eval()
-    directions_dir = opts.get('directions_dir', './directions')
     save_root = os.path.join(opts.get('save_dir', './results'), opts['name'])
-    steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     lr = float(inv.get('lr', 0.01))
     streams = int(inv.get('streams', 1))
     lpips_weight = float(inv.get('lpips_weight', 0.0))       # opt-in perceptual term of the W+ loss (oodgan/lpips.py)

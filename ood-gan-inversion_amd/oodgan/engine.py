@@ -77,6 +77,24 @@ def _pad_channels_to_16(state, prefix, log_size, ch):
     return out, chp
 
 
+def style_layout(log_size, channels_of):
+    """[(module name, latent index, row offset, channels)] of the (B, R) style tensor, in the generator's execution order (model.py:548-576):
+    conv1, to_rgb1, then convs.2j, convs.2j+1, to_rgbs.j per level; ``channels_of(name)``: the input channels of that modulated conv.  The one
+    definition of the order, for ``GeneratorEngine.style_layout`` and ``Generator.style_layout``.  Channel counts that are not multiples of 16
+    run zero-padded in the engine (its rows are then not the generator's): NotImplementedError."""
+    names = [('conv1', 0), ('to_rgb1', 1)]
+    for j in range(log_size - 2):
+        names += [(f'convs.{2 * j}', 2 * j + 1), (f'convs.{2 * j + 1}', 2 * j + 2), (f'to_rgbs.{j}', 2 * j + 3)]
+    out, row = [], 0
+    for name, lat in names:
+        n = int(channels_of(name))
+        if n % 16:
+            raise NotImplementedError(f'style_layout() of a generator whose channel counts are zero-padded to multiples of 16 ({name}: {n})')
+        out.append((name, lat, row, n))
+        row += n
+    return out
+
+
 class GeneratorEngine:
     def __init__(self, state, size, style_dim=512, channel_multiplier=2, prefix='', with_backward=True, precision=None, narrow=1,
                  blur_kernel=(1, 3, 3, 1), upsample_kernel=(1, 3, 3, 1)):
@@ -293,12 +311,20 @@ class GeneratorEngine:
         return self.bwd_flag is not None and int(self.bwd_flag.item()) != 0
 
     # ------------------------------------------------------------------ forward
-    def styles(self, latent):
-        """(B, n_latent, S) -> all style vectors (B, R) in one contraction."""
-        return ops.style_affine(latent, self.wcat, self.bcat, self.row_lat)
+    def styles(self, latent, offsets=None):
+        """(B, n_latent, S) -> all style vectors (B, R) in one contraction; ``offsets`` (B, R): StyleSpace offsets added to them."""
+        return ops.style_affine(latent, self.wcat, self.bcat, self.row_lat, offset=offsets)
+
+    def style_layout(self):
+        """[(layer name, latent index, first row, channels)] in row order: the meaning of a column of the (B, R) style tensor."""
+        if self.padded:
+            raise NotImplementedError('style_layout() of a generator whose channel counts are zero-padded to multiples of 16')
+        lay = style_layout(self.log_size, lambda name: self.by_name[name].cin)
+        assert lay == [(L.name, L.lat, L.row, L.cin) for L in self.layers]      # the rows the kernels use
+        return lay
 
     def forward(self, latent, noises, save=False, cond_hook=None, cond_layers=None, return_features=False, features_in=None,
-                feature_scale=1.0, range_mode='exact', post_hook=None):
+                feature_scale=1.0, range_mode='exact', post_hook=None, style_offsets=None):
         """latent (B,n_latent,S); noises list[num_layers] of (B|1,1,r,r).
         cond_hook(k, raw, latent_i, noise, noise_w) -> cond tensor replacing the raw up-conv output
         (the algebra of OOD_faceGAN_e4e_arch.py:239-242 + model.py:292: layer = cond + w*noise).
@@ -307,16 +333,20 @@ class GeneratorEngine:
         post_hook(k, out) -> tensor replacing the ACTIVATED output of the up-conv reading latent cond_layers[k]
         (feature_modulation for cond_type 'SFT' / 'ADD' / 'FUSE', model.py:558-566).
         range_mode (split-f16 only, ops.FwdRange): 'exact' measures max|x*s| of every conv input before converting it;
-        'carry' (the W+ loop) uses the scales of the previous forward with the fused producers and verifies them."""
+        'carry' (the W+ loop) uses the scales of the previous forward with the fused producers and verifies them.
+        style_offsets: float32 (B, R) added to the styles, s = style_affine(latent) + style_offsets (StyleSpace; the columns
+        are those of ``style_layout()``).  Everything downstream reads the sum; the hooks still receive the latent of their layer."""
         if self.padded and (cond_hook is not None or features_in is not None or post_hook is not None):
             raise NotImplementedError('conditioning hooks / feature injection on a generator whose channel counts are zero-padded to multiples of 16')
         if save and (features_in is not None or post_hook is not None):
             raise NotImplementedError('backward through an injected feature / feature modulation is not part of the path')
+        if self.padded and style_offsets is not None:
+            raise NotImplementedError('style offsets on a generator whose channel counts are zero-padded to multiples of 16')
         B = latent.shape[0]
         # forwards are counted: the activations saved for backward() live in pooled scratch buffers (ops.sform_scratch: keyed by shape and
         # stream) and their S-form scales alias the range state — ANY later forward of this engine on the same stream may overwrite them
         self._fwd_serial += 1
-        s_all = self.styles(latent)
+        s_all = self.styles(latent, style_offsets)
         d_all = torch.empty(B, self.DR, device=self.device, dtype=torch.float32)
         if self.batched_tail:       # the demodulation factors of all styled convs in one launch
             from ._lib import DemodFwdJob, lib, check
@@ -536,8 +566,10 @@ class GeneratorEngine:
                     and ops.s2_fuse_supported(B, L.cout, L.cin, 2 * Hd + 1, 2 * Hd + 1))
 
     # ------------------------------------------------------------------ backward (w.r.t. latents only)
-    def backward(self, gimg, grad_scale=1.0, carry_scale=False):
+    def backward(self, gimg, grad_scale=1.0, carry_scale=False, wrt='latent'):
         """gimg (B,3,size,size), already multiplied by ``grad_scale`` -> dL/dlatent (B,n_latent,S).
+        ``wrt='styles'``: dL/dstyles (B,R) instead — also the gradient of ``style_offsets`` — still multiplied by ``grad_scale``; the
+        contraction with the modulation matrices does not run.
         Needs forward(..., save=True).  Every step is linear in the gradient, so a power-of-two
         grad_scale is undone exactly at the end.
         ``carry_scale`` (set by the W+ loop): from the second call on, the activation gradients are produced directly
@@ -545,6 +577,8 @@ class GeneratorEngine:
         the caller must start a new sequence with reset_bwd_state() and check bwd_scale_violated() at its end."""
         from ._lib import lib, check
         import ctypes
+        if wrt not in ('latent', 'styles'):
+            raise ValueError(f"wrt must be 'latent' or 'styles', got {wrt!r}")
         sv = self.saved
         if sv is None:
             raise RuntimeError('backward() without forward(save=True)')
@@ -710,6 +744,8 @@ class GeneratorEngine:
         if jobs is not None:
             jobs.run(self.bwd_flag)         # four launches: partial sums, demodulation gradient, dot products, scale checks
         self.last_gs = gs_all
+        if wrt == 'styles':
+            return gs_all
         return ops.style_affine_backward(gs_all, self.wcat, self.lat_start, self.n_latent, grad_div=grad_scale)
 
 
@@ -784,7 +820,11 @@ class _WRun:
         # masked objective: the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
         # replays it unchanged; a rollback needs nothing new: it is constant for the run); None = the plain per-image MSE
         self.beta = beta
-        self.w = w0.detach().clone().contiguous()
+        # StyleSpace: the latents stay at their start, a persistent input like ``target``; the optimised state is the offset
+        # on the styles, (B, R), from 0.  It keeps the name ``w``: snapshots, rollback, trajectory and gathering work on it unchanged
+        self.sspace = inv.latent_space == 's'
+        self.w0 = w0.detach().clone().contiguous() if self.sspace else None
+        self.w = torch.zeros(w0.shape[0], eng.R, device=w0.device, dtype=torch.float32) if self.sspace else w0.detach().clone().contiguous()
         self.m, self.v = torch.zeros_like(self.w), torch.zeros_like(self.w)
         self.gmul = ops.loss_scale_for(target.numel() // target.shape[0])
         # the step index twice: ``t`` for the host's control flow, ``dev_t`` on the device for the step's kernels — the row of the loss tables
@@ -814,6 +854,8 @@ class _WRun:
         self.layer_lr = None if inv.layer_lr is None else torch.tensor(inv.layer_lr, dtype=torch.float32, device=self.w.device)
         self.dl_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.delta_reg != 0.0 else None
         self.controls = self.tied or self.layer_lr is not None or self.dl_table is not None
+        # ``style_reg`` brings a sixth loss table, mean_r delta_r^2 per step and image
+        self.st_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if (self.sspace and inv.style_reg != 0.0) else None
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
@@ -839,6 +881,16 @@ class _WRun:
     # ---- one W+ step on the current stream
     def _eager_step(self):
         eng, inv = self.eng, self.inv
+        if self.sspace:
+            # forward at style_affine(w0) + delta, the loss as ever, backward down to the styles — the contraction to dL/dW+ does not run, the
+            # step is one launch shorter than the W+ step — and the division by the loss scale, the regulariser and Adam in one kernel
+            img = eng.forward(self.w0, self.noises, save=True, range_mode='carry', style_offsets=self.w)
+            gimg = self._loss_grad(img)
+            gs = eng.backward(gimg, self.gmul, carry_scale=True, wrt='styles')
+            ops.style_step(self.w, gs, self.m, self.v, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown, inv.lr, inv.betas, inv.eps,
+                           grad_div=self.gmul, row_lat=eng.row_lat if self.layer_lr is not None else None, layer_lr=self.layer_lr,
+                           style_reg=inv.style_reg, table=self.st_table)
+            return
         w_in = self.w
         if self.w_in is not None:
             # W: one vector of noise per image, repeated over the layers — the rows of w_in stay identical
@@ -1047,11 +1099,12 @@ def check_pixel_loss(pixel_loss, pixel_scale, name='pixel_loss', scale_name='pix
     return pixel_loss, s.item()
 
 
-LATENT_SPACES = ('w+', 'w')
+LATENT_SPACES = ('w+', 'w', 's')
 
 
 def check_latent_space(value, name='latent_space'):
-    """Where the W+ loop moves: 'w+' (default: every layer its own vector) or 'w' (one vector per image); anything else raises ValueError."""
+    """Where the W+ loop moves: 'w+' (default: every layer its own vector), 'w' (one vector per image) or 's' (StyleSpace: an offset on the
+    per-channel styles, the latents fixed); anything else raises ValueError."""
     if not isinstance(value, str) or value not in LATENT_SPACES:
         raise ValueError(f'{name} must be one of {list(LATENT_SPACES)}, got {value!r}')
     return value
@@ -1085,6 +1138,19 @@ def check_latent_controls(latent_space, layer_lr, delta_reg, n_layers=None, pref
     return space, rates, reg
 
 
+def check_style_space(latent_space, style_reg, delta_reg=0.0, latent_noise=0.0, latent_reg=0.0, prefix=''):
+    """``style_reg`` as a float, checked against the latent space: in 's' the latents do not move, so the terms and the noise that act on them
+    (delta_reg, latent_noise, latent_reg) raise ValueError there, and ``style_reg`` raises it anywhere else."""
+    reg = check_nonneg(style_reg, prefix + 'style_reg')
+    if latent_space == 's':
+        for value, name in ((delta_reg, 'delta_reg'), (latent_noise, 'latent_noise'), (latent_reg, 'latent_reg')):
+            if check_nonneg(value, prefix + name) != 0.0:
+                raise ValueError(f"{prefix}{name} with {prefix}latent_space 's': the latents stay at their start there, only the style offsets move")
+    elif reg != 0.0:
+        raise ValueError(f"{prefix}style_reg with {prefix}latent_space {latent_space!r}: the term acts on the style offsets of latent_space 's'")
+    return reg
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1115,13 +1181,19 @@ class WPlusInverter:
     0 freezes a layer.  ``delta_reg``: adds delta_reg * mean_le (w_le - mean_l w_le)^2 per image, the squared spread of the layers about their
     mean, at the unperturbed w (``last_terms['delta']``); W is its limit.  'w' with either of the other two raises ValueError.
 
+    StyleSpace (Wu et al., CVPR 2021).  ``latent_space='s'``: the latents stay at ``w0`` and the loop optimises an offset delta
+    (B, R) on the per-channel styles, s = style_affine(w0) + delta, from 0 (the columns: ``GeneratorEngine.style_layout()``); ``invert`` then
+    returns delta in the latents' place.  ``style_reg`` = lambda >= 0 adds lambda * mean_r delta_r^2 per image (``last_terms['style']``), a
+    build-defined pull towards styles some w can produce.  ``layer_lr`` applies to the style rows of each layer; the lr ramps apply;
+    delta_reg, latent_noise and latent_reg act on latents that do not move and raise ValueError, as ``style_reg`` does outside 's'.
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
-                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0):
+                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
         # the size the LPIPS term is taken at (DESIGN.md §14): None = the image's own, today's path; an int: the image and the target are
         # area-pooled to it first (the projectors' value is 256).  The image size is known in ``invert``: the part of the check that needs it runs there
@@ -1143,6 +1215,9 @@ class WPlusInverter:
         self.noise_seed, self.latent_reg = check_noise_seed(noise_seed), check_nonneg(latent_reg, 'latent_reg')
         # latent controls, all off by default: the step is then the launch list above.  The number of layers is known in ``invert``
         self.latent_space, self.layer_lr, self.delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg)
+        # StyleSpace: ``latent_space='s'`` optimises an offset on the styles; ``style_reg`` * mean_r delta_r^2 per image pulls it
+        # back towards styles some w can produce — a term of this build, as delta_reg is
+        self.style_reg = check_style_space(self.latent_space, style_reg, self.delta_reg, self.latent_noise, self.latent_reg)
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
@@ -1171,6 +1246,8 @@ class WPlusInverter:
         self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
         ids, anchor = self._sched_inputs(w0, noise_ids, latent_anchor)
         check_layer_lr(self.layer_lr, int(w0.shape[1]))
+        if self.latent_space == 's' and self.engine.padded:
+            raise NotImplementedError("latent_space 's' on a generator whose channel counts are zero-padded to multiples of 16")
         if self.latent_space == 'w':            # the start: the layer mean, on every layer (set-up, not the step)
             w0 = w0.detach().mean(dim=1, keepdim=True).expand_as(w0).contiguous()
         if loss_weight is not None:
@@ -1182,7 +1259,8 @@ class WPlusInverter:
         if B == 0:          # an empty shard (oodgan/parallel.py hands a rank with no images an empty batch): nothing to launch
             steps = 0
         if steps <= 0:
-            w = w0.detach().clone().contiguous()
+            w = (torch.zeros(B, self.engine.R, device=w0.device, dtype=torch.float32) if self.latent_space == 's'
+                 else w0.detach().clone().contiguous())
             empty = torch.empty(0, B, device=w0.device, dtype=torch.float32)
             return (w, empty, []) if return_trajectory else (w, empty)
         if return_trajectory:
@@ -1210,7 +1288,7 @@ class WPlusInverter:
                          (self.pixel_loss != 'mse', 'a robust pixel term'),
                          (self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0,
                           'the projector schedule (lr ramps, latent noise, latent prior)'),
-                         (self.latent_space != 'w+', "latent_space 'w'"),
+                         (self.latent_space != 'w+', f'latent_space {self.latent_space!r}'),
                          (self.layer_lr is not None, 'layer_lr'),
                          (self.delta_reg != 0.0, 'delta_reg')):
             if on:
@@ -1300,16 +1378,18 @@ class WPlusInverter:
         self.last_stats = {'steps_run': [r.steps_run for r in runs], 'rollbacks': [r.rollbacks for r in runs]}
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
-                                                             [r.lat_table for r in runs], [r.dl_table for r in runs]])
+                                                             [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs]])
         # a graph run has no per-window guard: its flags are read once, here, and a flagged inversion is repeated through the guarded loop
         if use_graph and any(eng.bwd_scale_violated() or eng.fwd_range_violated() for eng in engines):
             return self.invert(target, w0, noises, steps, streams=streams, use_graph=False)
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None, dl=None):
-        self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl}
+    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None):
+        self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl,
+                           'style': st}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         total = total if lat is None else total + self.latent_reg * lat
-        return total if dl is None else total + self.delta_reg * dl
+        total = total if dl is None else total + self.delta_reg * dl
+        return total if st is None else total + self.style_reg * st

@@ -267,6 +267,15 @@ class Generator(nn.Module):
             self._engine_key = key
         return self._engine_obj
 
+    def style_layout(self):
+        """[(module name, latent index, row offset, channels)] in the engine's row order: the public meaning of a column of the (B, R) style
+        tensor, and of the StyleSpace offsets ``forward(style_offsets=)`` and ``invert(latent_space='s')`` work on.  Module
+        names are those of the state dict (``<name>.conv.modulation.bias`` is the bias an offset on that slice adds to); the latent
+        indexing is model.py:548-576.  Available without a GPU; the order is defined once, in ``engine.style_layout``, which the engine uses
+        too.  A generator whose channel counts the engine zero-pads (``narrow``) raises NotImplementedError, as its engine does."""
+        from .engine import style_layout
+        return style_layout(self.log_size, lambda name: self.get_submodule(name).conv.modulation.weight.shape[0])
+
     def make_noise(self):
         dev = self.input.input.device
         noises = [torch.randn(1, 1, 4, 4, device=dev)]
@@ -367,6 +376,8 @@ class Generator(nn.Module):
         eng = self.engine()
         kw = dict(cond_hook=hook, cond_layers=cl, return_features=want_feat, post_hook=post,
                   features_in=kwargs.get('features_in', None), feature_scale=kwargs.get('feature_scale', 1.0))
+        if kwargs.get('style_offsets', None) is not None:       # StyleSpace offsets (B, R), columns as ``style_layout()``; hooks still get the latents
+            kw['style_offsets'] = kwargs['style_offsets']
         # CARRY_FORWARD (opt-in): forward range scales (split-f16 path) carried from the previous forward of this batch size — the W+ loop's scheme
         # (engine.py, ops.FwdRange) for model(x) too: no measurement pass per conv input, the fused producers of the loop.  Scales are powers of two
         # and exact as long as the carried scale keeps the new maximum inside [1, 2^15) — if it does not, the flag is set and the pass
@@ -477,9 +488,13 @@ class StyleGAN2Generator(nn.Module):
     def latent_std(self, n=10000, seed=0):
         return self._inner[0].latent_std(n, seed)
 
+    def style_layout(self):
+        """``Generator.style_layout``: (module name in the reference generator's layout, latent index, row offset, channels) per style slice."""
+        return self._inner[0].style_layout()
+
     def forward(self, styles, input_is_latent=False, input_is_tensor=False, noise=None, randomize_noise=True, truncation=1,
                 truncation_latent=None, inject_index=None, return_latents=False, conditions=None, cond_layers=None,
-                cond_weights=None, cond_type='SFT'):
+                cond_weights=None, cond_type='SFT', style_offsets=None):
         if cond_layers is not None and conditions is not None and cond_type == 'NOISE':
             raise NotImplementedError('unknown mod_type NOISE')      # feature_modulation raises the same (stylegan2_arch.py:594)
         # reference quirk (stylegan2_arch.py:555,570): input_is_latent alone skips the MLP *and* the broadcast
@@ -488,4 +503,4 @@ class StyleGAN2Generator(nn.Module):
         return self._inner[0](styles, return_latents=return_latents, inject_index=inject_index, truncation=truncation,
                               truncation_latent=truncation_latent, input_is_latent=input_is_latent,
                               input_is_tensor=input_is_tensor, noise=noise, randomize_noise=randomize_noise,
-                              conditions=conditions, cond_layers=cond_layers, cond_type=cond_type)
+                              conditions=conditions, cond_layers=cond_layers, cond_type=cond_type, style_offsets=style_offsets)

@@ -178,8 +178,9 @@ def feature_modulation(gen_feats, conditions, clss=None, mod_type='SFT'):
 
 
 # ----------------------------------------------------------------------------- style path
-def style_affine(latent, wcat, bcat=None, row_lat=None, lr_mul=1.0):
-    """s[b,r] = (1/sqrt(S)) * lr_mul * W[r]·latent[b,row_lat[r]] + bias[r]*lr_mul  (EqualLinear, model.py:129-158)."""
+def style_affine(latent, wcat, bcat=None, row_lat=None, lr_mul=1.0, offset=None):
+    """s[b,r] = (1/sqrt(S)) * lr_mul * W[r]·latent[b,row_lat[r]] + bias[r]*lr_mul  (EqualLinear, model.py:129-158).
+    ``offset``: float32 (B,R), added to the rounded style (oodgan_style_affine_fwd_offset, the StyleSpace offsets of DESIGN.md §19)."""
     lat = _dev(latent, 'latent')
     if lat.ndim == 2:
         lat = lat.unsqueeze(1)
@@ -188,6 +189,13 @@ def style_affine(latent, wcat, bcat=None, row_lat=None, lr_mul=1.0):
     R = w.shape[0]
     s = torch.empty(B, R, device=lat.device, dtype=torch.float32)
     scale = (1.0 / math.sqrt(S)) * lr_mul
+    if offset is not None:
+        off = _dev(offset, 'offset')
+        if tuple(off.shape) != (B, R):
+            raise ValueError(f'style_affine: offset must be ({B}, {R}), got {tuple(off.shape)}')
+        check(_lib.lib().oodgan_style_affine_fwd_offset(_p(lat.contiguous()), _p(w), _p(_opt(bcat, 'bcat')), _p(row_lat), _p(off), _p(s), B, L,
+                                                        S, R, scale, float(lr_mul), _stream()), 'style_affine_fwd_offset')
+        return s
     check(_lib.lib().oodgan_style_affine_fwd(_p(lat.contiguous()), _p(w), _p(_opt(bcat, 'bcat')), _p(row_lat), _p(s), B, L, S, R,
                                              scale, float(lr_mul), _stream()), 'style_affine_fwd')
     return s
@@ -1541,3 +1549,56 @@ def latent_step(w, g, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.0
                                         int(total_steps), float(rampup), float(rampdown), _p(layer_lr), float(delta_reg), int(bool(tied)),
                                         _p(dst), nrows, _stream()), 'latent_step')
     return w
+
+
+# ---- StyleSpace step of the W+ loop (csrc/wplus_sched.hip)
+_ROW_LAT_MAX = {}
+
+
+def _row_lat_max(row_lat):
+    """The largest latent index ``row_lat`` names: one device-to-host read per (buffer, version) — the loop passes the engine's table every step."""
+    key = (row_lat.data_ptr(), row_lat._version, row_lat.numel())
+    if key not in _ROW_LAT_MAX:
+        _ROW_LAT_MAX.clear()
+        _ROW_LAT_MAX[key] = int(row_lat.max().item())
+    return _ROW_LAT_MAX[key]
+
+
+def style_step(delta, gs, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.01, betas=(0.9, 0.999), eps=1e-8, grad_div=1.0, row_lat=None,
+               layer_lr=None, style_reg=0.0, table=None, loss_out=None):
+    """``adam_step_dev_sched`` on the style offsets (oodgan_style_step): delta, gs, m, v (B, R), all contiguous float32 and updated in place.
+    ``gs`` is dL/ds times ``grad_div`` (``GeneratorEngine.backward(wrt='styles')``); the step divides it first.  ``style_reg`` = lambda:
+    g += lambda * dR/ddelta for R_b = mean_r delta_r^2; ``layer_lr``: float32 (L,) on the device, a factor of the step size per latent, applied
+    to style row r through ``row_lat`` (int32 (R,): the latent the row reads); 0 freezes those rows.  gs holds afterwards what Adam consumed.
+    R goes to row t_dev[0] (before the increment, clamped) of ``table`` (nrows, B), or to ``loss_out`` (B,); with neither it is not written.
+    grad_div 1 and nothing on: the bits of ``adam_step_dev_sched``.  Returns delta."""
+    a = _dev(delta, 'delta')
+    if a.dim() != 2:
+        raise ValueError(f'style_step: delta must be (B, R), got {tuple(a.shape)}')
+    B, R = a.shape
+    for t, name in ((delta, 'delta'), (gs, 'gs'), (m, 'm'), (v, 'v')):
+        assert isinstance(t, torch.Tensor) and t.shape == a.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == a.device, \
+            f'style_step: {name} must be a contiguous float32 tensor of the offsets\' shape on their device (it is updated in place)'
+    assert t_dev.dtype == torch.int32 and t_dev.device == a.device
+    if row_lat is not None:
+        assert row_lat.shape == (R,) and row_lat.dtype == torch.int32 and row_lat.is_contiguous() and row_lat.device == a.device, \
+            f'style_step: row_lat must be a contiguous int32 ({R},) tensor on the offsets\' device'
+    if layer_lr is not None:
+        assert layer_lr.dim() == 1 and layer_lr.dtype == torch.float32 and layer_lr.is_contiguous() and layer_lr.device == a.device, \
+            'style_step: layer_lr must be a contiguous float32 (L,) tensor on the offsets\' device'
+        if row_lat is None:
+            raise ValueError('style_step: layer_lr needs row_lat, the latent each style row reads')
+        top = _row_lat_max(row_lat)
+        if layer_lr.numel() <= top:
+            raise ValueError(f'style_step: layer_lr has {layer_lr.numel()} entries, row_lat names latent {top}')
+    dst, nrows = None, 0
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and table.device == a.device
+        dst, nrows = table, table.shape[0]
+    elif loss_out is not None:
+        assert loss_out.shape == (B,) and loss_out.dtype == torch.float32 and loss_out.is_contiguous() and loss_out.device == a.device
+        dst, nrows = loss_out, 1
+    check(_lib.lib().oodgan_style_step(_p(delta), _p(gs), _p(m), _p(v), B, R, float(lr), float(betas[0]), float(betas[1]), float(eps), _p(t_dev),
+                                       int(total_steps), float(rampup), float(rampdown), float(grad_div), _p(row_lat), _p(layer_lr),
+                                       float(style_reg), _p(dst), nrows, _stream()), 'style_step')
+    return delta
