@@ -60,7 +60,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]) and "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) and "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);
@@ -663,6 +663,25 @@ int oodgan_robust_loss_fwd_bwd_row(const float* img, const float* target, const 
  * dispatch counter "area_pool". */
 int oodgan_area_pool_fwd(const float* x, float* y, float* gzero, int BC, int H, int W, int f, void* stream);
 int oodgan_area_pool_bwd_add(const float* gs, float* gimg, int BC, int H, int W, int f, void* stream);
+/* The pixel term on an area-pooled view (the W+ loop's pixel_size): img (B,C,H,W), f in {2, 4, 8, 16}, Hs = H/f, Ws = W/f,
+ * P = the window mean exactly as oodgan_area_pool_fwd forms it.  Pooled residual: beta NULL: r = P(img) - target_pooled, target_pooled
+ * (B,C,Hs,Ws) = P(target) made once by the caller, `target` NULL; with beta (B,1,H,W): r = P(beta*(img - target)) — per pixel two roundings, as
+ * the unpooled composite — from the full `target`, target_pooled NULL.  loss[b] = mean over C*Hs*Ws of rho(r); kind 0 = the square, else an
+ * OODGAN_ROBUST_* kind at `scale` (rho, psi as oodgan_robust_loss_fwd_bwd).  gimg (B,C,H,W) or NULL (forward only, the same loss bit for
+ * bit): every pixel of window q receives gscale * psi(r_q), gscale = grad_mul/(C*H*W) (twice that for the square: the magnitude of the
+ * unpooled term), with beta and wrt_gen = 1 times beta(y,x).  comp (B,C,H,W) or NULL receives c = target + beta*(img - target) at full
+ * resolution (needs beta).  part: (B, oodgan_pooled_pixel_loss_nparts(C*Hs*Ws, f)) scratch; one thread owns a window in both directions,
+ * two-stage sums, no float atomics: bit-reproducible.  OODGAN_E_ARG with a message, nothing launched, for another factor, a plane that
+ * is no multiple of it, a full-resolution pointer not aligned to 8 (f = 2) or 16 bytes, comp without beta, an unknown kind, a bad
+ * scale, and target / target_pooled not as the form needs them.  Counted by the dispatch counter "pooled_pixel". */
+int oodgan_pooled_pixel_loss_fwd_bwd(const float* img, const float* target, const float* target_pooled, const float* beta, float* gimg,
+                                     float* comp, float* part, float* loss, int B, int C, int H, int W, int f, int kind, float scale,
+                                     int wrt_gen, float grad_mul, void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_pooled_pixel_loss_fwd_bwd_row(const float* img, const float* target, const float* target_pooled, const float* beta, float* gimg,
+                                         float* comp, float* part, float* loss_table, const int* row_dev, int nrows, int B, int C, int H,
+                                         int W, int f, int kind, float scale, int wrt_gen, float grad_mul, void* stream);
+int oodgan_pooled_pixel_loss_nparts(long CHWs, int f);
 /* torch.optim.Adam step (no weight decay, no amsgrad), step index t>=1 given by the host:
  * anchors: get_optimizer (src/models/OOD_faceGAN_model.py:398-400). */
 int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,

@@ -28,4 +28,23 @@ __global__ __launch_bounds__(64) void mean_finish_kernel(const T* __restrict__ p
     if (lane == 0) loss[row + b] = s * inv_n;
 }
 
+// ---- F x F windows of the area pool (loss_pool.hip) and of the pooled pixel term (loss_pixel.hip): one thread owns a window
+template <int F>
+struct Row {                                     // the vector a window row is read in, and how many of them a row has
+    using V = float4;
+    static constexpr int N = F / 4;
+};
+template <>
+struct Row<2> {
+    using V = float2;
+    static constexpr int N = 1;
+};
+
+// the window's sum: fp32, row-major order, never reassociated
+__device__ __forceinline__ float sum_in_order(float acc, const float2 v) { return (acc + v.x) + v.y; }
+__device__ __forceinline__ float sum_in_order(float acc, const float4 v) { return (((acc + v.x) + v.y) + v.z) + v.w; }
+
+// what a full-resolution pointer must be aligned to for the row vectors of factor f (W % f == 0 then aligns every window row)
+inline int pool_row_align(int f) { return f == 2 ? 8 : 16; }
+
 }  // namespace oodgan

@@ -14,19 +14,7 @@ using namespace oodgan;
 
 namespace {
 
-template <int F>
-struct Row {                                     // the vector a window row is read in, and how many of them a row has
-    using V = float4;
-    static constexpr int N = F / 4;
-};
-template <>
-struct Row<2> {
-    using V = float2;
-    static constexpr int N = 1;
-};
-
-__device__ __forceinline__ float sum_in_order(float acc, const float2 v) { return (acc + v.x) + v.y; }
-__device__ __forceinline__ float sum_in_order(float acc, const float4 v) { return (((acc + v.x) + v.y) + v.z) + v.w; }
+// Row<F>, sum_in_order: loss_common.hpp (the pooled pixel term of loss_pixel.hip walks a window the same way)
 __device__ __forceinline__ float2 add_all(float2 v, float g) { return make_float2(v.x + g, v.y + g); }
 __device__ __forceinline__ float4 add_all(float4 v, float g) { return make_float4(v.x + g, v.y + g, v.z + g, v.w + g); }
 
@@ -90,8 +78,8 @@ int check_shape(const char* what, const void* full, int BC, int H, int W, int f,
     OODGAN_REQUIRE(f == 2 || f == 4 || f == 8 || f == 16, "%s: factor %d: must be 2, 4, 8 or 16", what, f);
     OODGAN_REQUIRE(BC > 0 && H > 0 && W > 0, "%s: bad shape (%d, %d, %d)", what, BC, H, W);
     OODGAN_REQUIRE(H % f == 0 && W % f == 0, "%s: a %dx%d plane is not a multiple of the factor %d", what, H, W, f);
-    OODGAN_REQUIRE(reinterpret_cast<uintptr_t>(full) % (f == 2 ? 8 : 16) == 0, "%s: the full-resolution tensor must be %d-byte aligned", what,
-                   f == 2 ? 8 : 16);
+    OODGAN_REQUIRE(reinterpret_cast<uintptr_t>(full) % pool_row_align(f) == 0, "%s: the full-resolution tensor must be %d-byte aligned", what,
+                   pool_row_align(f));
     *total = (long)BC * (H / f) * (W / f);
     OODGAN_REQUIRE((*total + 255) / 256 <= 0x7fffffffL, "%s: %ld pooled pixels: too many for one grid", what, *total);
     return OODGAN_OK;

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg
 from .modules import Generator
 from .synth import generator_channels
 
@@ -265,7 +265,7 @@ class ood_faceGAN_e4e(nn.Module):
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
-               delta_reg=0.0, style_reg=0.0, **kwargs):
+               delta_reg=0.0, style_reg=0.0, pixel_size=None, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -308,6 +308,15 @@ class ood_faceGAN_e4e(nn.Module):
         and SSIM terms stay at full resolution.  256 is the projectors' value (rosinality's projector.py and the StyleGAN2-ADA projector pool
         to 256² before LPIPS): AlexNet's fields then cover facial structure, and the term costs a fraction of its full-resolution time.
         A value that is not an int, is below 64, or does not divide the image size by one of those factors raises ValueError.
+        ``pixel_size``: the size the pixel term is taken at.  None (default) or the image's own size: the path above unchanged.
+        An int: the term is the mean of rho over the residual of the area-pooled views, P(G) - P(x) (with ``loss_region``: P(beta*(G - x)), the
+        pooled composite minus the pooled target), f = size / pixel_size in {2, 4, 8, 16}; every pixel of a window receives its window's
+        gradient, at the magnitude of the full-resolution term.  One fused kernel, no more launches per step.  With ``lpips_size`` of the same
+        value both terms see one view (256: the projectors' horizon), and detail the generator cannot produce — hair strands, sensor noise, JPEG
+        blocks — stops pulling the latent.  A low-resolution photograph is inverted by passing it nearest-upsampled to the generator's size with
+        ``pixel_size`` = its own size: the area pool of a nearest-upsampled image is the image itself, so the term compares pool(G) with exactly
+        the pixels there are, while the encoder and the OOD forward keep their full-size input.  A value that is not an int or does not divide the
+        image size by one of those factors raises ValueError; ``use_graph`` with it NotImplementedError.
         ``edit``: an editing direction applied AFTER the fit — a float32 (L,512), (1,L,512) or (B,L,512) tensor on the model's
         device.  The loop runs exactly as without it (the same ``losses``, the same refined latents w); the final OOD forward is taken at w + edit
         and the returned ``lats`` are those latents, the ones the output was generated from.  ``self.last_refined_lats`` holds w after every call,
@@ -337,6 +346,7 @@ class ood_faceGAN_e4e(nn.Module):
         noise_seed, latent_reg = check_noise_seed(noise_seed), check_nonneg(latent_reg, 'latent_reg')
         pixel_loss, pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
         lpips_size = check_lpips_size(lpips_size, int(x.shape[-1]))
+        pixel_size = check_pixel_size(pixel_size, int(x.shape[-1]))
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         latent_space, layer_lr, delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg, self.generator.n_latent)
@@ -370,7 +380,7 @@ class ood_faceGAN_e4e(nn.Module):
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
-                            delta_reg=delta_reg, style_reg=style_reg)
+                            delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
                                latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan

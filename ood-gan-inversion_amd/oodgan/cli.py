@@ -30,6 +30,10 @@ Where the W+ loss looks, in the same block:
     lpips_size: <int>            the size the LPIPS term (``lpips_weight``) is taken at: the image and the target are area-pooled to
                                  it first; the projectors' value is 256.  Absent (default): the image's own size.  It must be >= 64 and divide the
                                  generator size by 1, 2, 4, 8 or 16; anything else is an error.
+    pixel_size: <int>            the size the pixel term is taken at: the mean of rho over the residual of the area-pooled image
+                                 and target, one fused kernel.  Absent (default) or the generator size: the full-resolution term.  It must divide
+                                 the generator size by 1, 2, 4, 8 or 16; anything else is an error.  For a low-resolution photograph: feed it
+                                 nearest-upsampled and give its own size here.
 The projector schedule of the W+ loop (rosinality's projector.py), in the same block, everything off by default:
 
     lr_rampup, lr_rampdown: <f>  fractions of the run over which the learning rate ramps up linearly / follows a cosine down (projector: 0.05, 0.25)
@@ -77,7 +81,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_nonneg
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -320,6 +324,7 @@ def run(opts, wplus_steps=None, log=None):
                                                'inversion.pixel_scale')
     out_size = (opts.get('network_g') or {}).get('out_size')
     lpips_size = check_lpips_size(inv.get('lpips_size'), out_size if isinstance(out_size, int) else None, 'inversion.lpips_size')
+    pixel_size = check_pixel_size(inv.get('pixel_size'), out_size if isinstance(out_size, int) else None, 'inversion.pixel_size')
     sched = schedule_options(inv)
     sched.update(latent_options(inv))
     sched.update(style_options(inv))
@@ -346,6 +351,7 @@ def run(opts, wplus_steps=None, log=None):
         graphed = GraphedForward(model)          # model(x) replayed from a hipGraph: -6 % latency per image at batch 1
     size = model.generator.size
     check_lpips_size(lpips_size, size, 'inversion.lpips_size')
+    pixel_size = check_pixel_size(pixel_size, size, 'inversion.pixel_size')
     latent_options(inv, model.generator.n_latent)
     summary = {}
     for name, dopt in opts['datasets'].items():
@@ -388,7 +394,7 @@ def run(opts, wplus_steps=None, log=None):
                     t0 = time.time()
                     if steps > 0:
                         out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
-                                           loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size,
+                                           loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, pixel_size=pixel_size,
                                            noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), edit=edit, **sched)[0]
                     else:
                         out = (graphed(x) if graphed is not None else model(x))[0]

@@ -838,6 +838,11 @@ class _WRun:
         self.lp_f = inv._lpips_f if self.lp is not None else 1
         self.lp_target = self.lp.target_taps(target if self.lp_f == 1 else ops.area_pool(target.contiguous(), self.lp_f)) if self.lp is not None else None
         self.lp_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if self.lp is not None else None
+        # ``pixel_size``: the pixel term on the area-pooled view, factor ``px_f``.  The pooled target is a persistent input like
+        # ``target`` and ``lp_target``, made here, once: never born inside a recorded step (see ``replay`` below), and the step reads it
+        # instead of the full target — with a loss weight the kernel pools beta*(G - x) from the full target and this stays None
+        self.px_f = inv._pixel_f
+        self.px_target = ops.area_pool(target.contiguous(), self.px_f) if (self.px_f > 1 and beta is None) else None
         # optional SSIM term (csrc/loss_ssim.hip): a third loss table, 1 - SSIM per step and image
         self.ss_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.ssim_weight != 0.0 else None
         # projector schedule (csrc/wplus_sched.hip).  ``w_in``, the perturbed latent the generator reads, is a persistent
@@ -914,11 +919,12 @@ class _WRun:
         they accumulate into the gradient: the pixel term (the MSE, or the robust term ``pixel_loss`` names) writes it, LPIPS and 1 - SSIM add
         lambda * gmul * their part; with ``lpips_size`` LPIPS is taken on the area-pooled view of the same image.  With a loss weight beta
         the terms are taken on the composite c: alone, the composite MSE writes beta*dL/dc in one kernel; with LPIPS or
-        SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards."""
+        SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards.  With ``pixel_size`` the pixel term is the fused
+        kernel of the pooled view: the same call, the same number of launches, a full-resolution gradient and composite."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
         on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
         _, gimg, c = ops.pixel_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if on_c else 'gen',
-                                         composite=on_c, table=self.lbuf, row_dev=row)
+                                         composite=on_c, table=self.lbuf, row_dev=row, pool=self.px_f, target_pooled=self.px_target)
         x = c if on_c else img
         if self.lp is not None and self.lp_f == 1:
             self.lp.loss_and_grad(x, gimg, inv.lpips_weight * gmul, table=self.lp_table, row_dev=row, target_taps=self.lp_target)
@@ -1081,6 +1087,27 @@ def check_lpips_size(value, image_size=None, name='lpips_size'):
     return value
 
 
+PIXEL_POOL_FACTORS = (1, 2, 4, 8, 16)      # 1: full resolution; the others: the factors of the pooled pixel kernel (csrc/loss_pixel.hip)
+
+
+def check_pixel_size(value, image_size=None, name='pixel_size'):
+    """The size the pixel term is taken at (None: the image's own): ValueError unless it is None or a positive int (not a bool) and, once the
+    image size is known, a divisor of it with a quotient in PIXEL_POOL_FACTORS — the only lower bound.  Returns the value, None for the
+    image's own size (factor 1: today's path)."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int):
+        raise ValueError(f'{name} must be None or an int, got {value!r}')
+    if value < 1:
+        raise ValueError(f'{name} must be positive, got {value!r}')
+    if image_size is not None:
+        if value > image_size or image_size % value != 0 or image_size // value not in PIXEL_POOL_FACTORS:
+            raise ValueError(f'{name} must divide the image size {image_size} by one of {list(PIXEL_POOL_FACTORS)}, got {value!r}')
+        if value == image_size:
+            return None
+    return value
+
+
 PIXEL_LOSSES = ('mse',) + tuple(ops.ROBUST_KINDS)
 
 
@@ -1164,7 +1191,7 @@ class WPlusInverter:
     ``noise=<list>`` (model.py:483-585), torch.optim.Adam as built by get_optimizer
     (src/models/OOD_faceGAN_model.py:398-400), basicsr MSELoss (losses.py:58-83).
 
-    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight) — + lpips_weight * LPIPS
+    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight; with ``pixel_size`` on the view area-pooled to that size) — + lpips_weight * LPIPS
     (with ``lpips_size`` on the image and the target area-pooled to that size) + ssim_weight * (1 - SSIM); the step index is a device counter in every mode.
     The step itself is defined once too, ``_WRun._eager_step``: run from Python, replayed from a launch plan (default) or, with
     ``invert(use_graph=True)``, from a captured hipGraph, with a trajectory or without, on any number of streams.
@@ -1193,8 +1220,13 @@ class WPlusInverter:
 
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
-                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0):
+                 pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
+                 pixel_size=None):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # the size the pixel term is taken at: None = the image's own, today's kernels and launch list; an int: the term is the
+        # mean of rho over the area-pooled residual (one fused kernel; with ``lpips_size`` of the same value both terms see one view).  A
+        # low-resolution photograph enters nearest-upsampled: its area pool is the photograph.  Checked against the image size in ``invert``
+        self.pixel_size, self._pixel_f = check_pixel_size(pixel_size), 1
         # the size the LPIPS term is taken at: None = the image's own, today's path; an int: the image and the target are
         # area-pooled to it first (the projectors' value is 256).  The image size is known in ``invert``: the part of the check that needs it runs there
         self.lpips_size, self._lpips_f = check_lpips_size(lpips_size), 1
@@ -1244,6 +1276,10 @@ class WPlusInverter:
         B = w0.shape[0]
         size = check_lpips_size(self.lpips_size, int(target.shape[-1]))
         self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
+        psize = check_pixel_size(self.pixel_size, int(target.shape[-1]))
+        self._pixel_f = 1 if psize is None else int(target.shape[-1]) // psize
+        if self._pixel_f > 1 and (target.shape[-2] % self._pixel_f or target.shape[-1] % self._pixel_f):
+            raise ValueError(f'pixel_size {self.pixel_size}: the image {tuple(target.shape[-2:])} is not a multiple of the factor {self._pixel_f}')
         ids, anchor = self._sched_inputs(w0, noise_ids, latent_anchor)
         check_layer_lr(self.layer_lr, int(w0.shape[1]))
         if self.latent_space == 's' and self.engine.padded:
@@ -1286,6 +1322,7 @@ class WPlusInverter:
                          (self.lpips is not None and self.lpips_weight != 0.0, 'the LPIPS term'),
                          (self.ssim_weight != 0.0, 'the SSIM term'),
                          (self.pixel_loss != 'mse', 'a robust pixel term'),
+                         (self._pixel_f > 1, 'pixel_size'),
                          (self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0,
                           'the projector schedule (lr ramps, latent noise, latent prior)'),
                          (self.latent_space != 'w+', f'latent_space {self.latent_space!r}'),

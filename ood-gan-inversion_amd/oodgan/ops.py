@@ -1242,7 +1242,7 @@ ROBUST_KINDS = {'charbonnier': 1, 'huber': 2, 'geman_mcclure': 3}
 
 
 def pixel_loss_grad(img, target, kind='mse', scale=None, beta=None, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None,
-                    row_dev=None, grad=True):
+                    row_dev=None, grad=True, pool=1, target_pooled=None):
     """The pixel term of the W+ loss (csrc/loss_pixel.hip): per-image mean of rho(d), d = img - target or, with a loss weight
     ``beta`` (B,1,H,W), d = beta*(img - target) on the composite c = target + d (the masked objective).  ``kind``: 'mse' (rho = d^2; the gradient
     is grad_mul*2/CHW * d) or a robust term at ``scale`` s > 0, used as a float32 (the gradient is grad_mul/CHW * rho'(d)): 'charbonnier'
@@ -1252,10 +1252,19 @@ def pixel_loss_grad(img, target, kind='mse', scale=None, beta=None, grad_mul=1.0
     The plain MSE takes any (B, ...) shape, every other form (B,C,H,W).  Returns (loss[B] or None with ``table``, gimg or None, c or None).
     ``loss_out``: a contiguous float32 (B,) view that receives the losses.  ``table`` (nrows, B) + ``row_dev`` (int32[1] on the device): the losses
     go to row row_dev[0] of the table (the ``_row`` entry points: the W+ loop's loss table, a recorded step writes a new row on every replay).
-    One kernel family behind the three entry points: beta == 1 gives the plain form's loss and gradient bit for bit."""
+    One kernel family behind the three entry points: beta == 1 gives the plain form's loss and gradient bit for bit.
+    ``pool`` = f in {2, 4, 8, 16}: the term on the area-pooled view, one fused kernel (oodgan_pooled_pixel_loss_fwd_bwd) — the
+    residual is r = area_pool(img) - ``target_pooled`` (``area_pool(target, f)``, made once by the caller; left out, it is pooled here, a
+    convenience outside a step) or, with beta, r = area_pool(beta*(img - target)); the loss is the mean of rho(r) over the pooled pixels and
+    every pixel of a window receives gscale * rho'(r) of its window, gscale as above (times beta(y,x) with ``wrt='gen'``); the gradient
+    and the composite stay (B,C,H,W).  ``pool=1`` (default) is the path above, untouched."""
     a, t = _dev(img, 'img'), _dev(target, 'target')
     if kind != 'mse' and kind not in ROBUST_KINDS:
         raise ValueError(f"kind must be 'mse' or one of {sorted(ROBUST_KINDS)}, got {kind!r}")
+    if _pool_factor(pool) > 1:
+        return _pooled_pixel_loss_grad(a, t, kind, scale, beta, grad_mul, wrt, composite, loss_out, table, row_dev, grad, pool, target_pooled)
+    if target_pooled is not None:
+        raise ValueError('target_pooled is the pooled target of pool > 1')
     entry = 'robust_loss' if kind != 'mse' else 'mse' if beta is None else 'composite_mse'
     if entry != 'mse' and (a.dim() != 4 or a.shape != t.shape):
         raise ValueError(f'{entry}_grad: img and target must be (B,C,H,W) of one shape, got {tuple(a.shape)} and {tuple(t.shape)}')
@@ -1282,6 +1291,36 @@ def pixel_loss_grad(img, target, kind='mse', scale=None, beta=None, grad_mul=1.0
         args += (1 if wrt == 'gen' else 0,)
     name = entry + ('_row' if by_row else '')
     check(getattr(L, f'oodgan_{entry}_fwd_bwd' + ('_row' if by_row else ''))(*args, float(grad_mul), _stream()), name)
+    return loss, g, c
+
+
+def _pooled_pixel_loss_grad(a, t, kind, scale, beta, grad_mul, wrt, composite, loss_out, table, row_dev, grad, f, target_pooled):
+    """``pixel_loss_grad`` with ``pool`` = f > 1: the fused kernel of the pooled view."""
+    if a.dim() != 4 or a.shape != t.shape:
+        raise ValueError(f'pooled pixel term: img and target must be (B,C,H,W) of one shape, got {tuple(a.shape)} and {tuple(t.shape)}')
+    if wrt not in ('gen', 'composite'):
+        raise ValueError(f"wrt must be 'gen' or 'composite', got {wrt!r}")
+    w = None if beta is None else _plane(beta, a)
+    if composite and w is None:
+        raise ValueError('composite=True needs beta: without a loss weight the composite is the image')
+    B, C, H, W = a.shape
+    ts = None
+    if w is None:
+        ts = area_pool(t, f) if target_pooled is None else _dev(target_pooled, 'target_pooled')
+        if tuple(ts.shape) != (B, C, H // f, W // f) or ts.device != a.device:
+            raise ValueError(f'target_pooled must have shape {(B, C, H // f, W // f)} on {a.device}, got {tuple(ts.shape)} on {ts.device}')
+    elif target_pooled is not None:
+        raise ValueError('with beta the residual is pooled from the full target: target_pooled must be None')
+    L = _lib.lib()
+    part = torch.empty(B, max(1, L.oodgan_pooled_pixel_loss_nparts(C * (H // f) * (W // f), f)), device=a.device, dtype=torch.float32)
+    g = torch.empty_like(a) if grad else None
+    c = torch.empty_like(a) if composite else None
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    sink = (_p(dst), _p(row), nrows) if by_row else (_p(dst),)
+    name = 'pooled_pixel_loss_fwd_bwd' + ('_row' if by_row else '')
+    check(getattr(L, 'oodgan_' + name)(_p(a), _p(t) if w is not None else None, _p(ts), _p(w), _p(g), _p(c), _p(part), *sink, B, C, H, W, f,
+                                       0 if kind == 'mse' else ROBUST_KINDS[kind], 0.0 if kind == 'mse' else float(scale),
+                                       1 if wrt == 'gen' else 0, float(grad_mul), _stream()), name)
     return loss, g, c
 
 
