@@ -746,6 +746,29 @@ int oodgan_latent_step(float* w, float* g, float* m, float* v, int B, int L, int
 int oodgan_style_step(float* delta, float* gs, float* m, float* v, int B, int R, float lr, float beta1, float beta2, float eps, int* t_dev,
                       int total_steps, float rampup, float rampdown, float grad_div, const int* row_lat, const float* layer_lr,
                       float style_reg, float* reg_table, int nrows, void* stream);
+/* Feature offset of the W+ loop (csrc/feature_offset.hip; ABI 115): beside the latents the loop optimises an offset delta
+ * (B, C, h, h), float32, from 0, on the input of the styled up-conv that reads latent `feature_layer`: x' = x(w) + delta.
+ * y = x + delta for n floats: one fp32 addition per element, 16 bytes per lane where x, delta and y are 16-byte aligned (the n % 4 last
+ * elements one by one), element by element otherwise.  y may be x.  A launch of this library, so that a launch plan replays it. */
+int oodgan_feature_add(const float* x, const float* delta, float* y, long n, void* stream);
+/* Partial sums per image of oodgan_feature_step (one per block of 4096 elements); 0: n_per_image <= 0 or too large. */
+int oodgan_feature_step_nparts(long n_per_image);
+/* The feature side of a step: delta, g, m, v (B, n_per_image); g is dL/dx' as the backward pass leaves it, times the loss scale grad_div.
+ * Launched BEFORE the latent-side call of the same step (oodgan_adam_step_dev[_sched], oodgan_latent_step), which increments the counter:
+ * this entry reads t_dev[0], does NOT increment it, and uses t = t_dev[0] + 1.  Per element:
+ *   g = g / grad_div (a correctly rounded division);
+ *   R_b = mean delta^2 of image b, before the update (double sums in two deterministic stages: one partial per block to `part`
+ *   (B, oodgan_feature_step_nparts) doubles, then one wave per image; rounded once), written to row min(t - 1, nrows - 1) of reg_table
+ *   (nrows, B); reg_table NULL: not written, and `part` is not touched and may be NULL — reg_table without `part` is refused (-1);
+ *   feature_reg > 0: g += 2 feature_reg / n_per_image * delta (the gradient of feature_reg * R_b);
+ *   g is written back: it holds what Adam consumed;
+ *   Adam as oodgan_adam_step_dev_sched, the same ramp factor r(t - 1) in double.
+ * Vectorised (16 bytes per lane) where n_per_image % 4 == 0 and the four pointers are 16-byte aligned.  No atomics: bit-reproducible.
+ * grad_div 1, feature_reg 0 and reg_table NULL: delta, m, v bit-identical to oodgan_adam_step_dev_sched run on the same buffers from the
+ * same counter value.  feature_reg * R_b keeps the offset small where the latents can explain the image; it is this build's own term. */
+int oodgan_feature_step(float* delta, float* g, float* m, float* v, int B, long n_per_image, float lr, float beta1, float beta2, float eps,
+                        const int* t_dev, int total_steps, float rampup, float rampdown, float grad_div, float feature_reg,
+                        float* reg_table, int nrows, double* part, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

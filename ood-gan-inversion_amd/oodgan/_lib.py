@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 114
+ABI_VERSION = 115
 
 
 class ConvArgs(Structure):
@@ -190,6 +190,10 @@ _SIGS = {
                                    c_int, P, c_int, P]),
     'oodgan_style_step': (c_int, [P, P, P, P, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, c_float, P, P, c_float,
                                   P, c_int, P]),
+    'oodgan_feature_add': (c_int, [P, P, P, c_long, P]),
+    'oodgan_feature_step_nparts': (c_int, [c_long]),
+    'oodgan_feature_step': (c_int, [P, P, P, P, c_int, c_long, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, c_float, c_float, P,
+                                    c_int, P, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
     'oodgan_u8_to_input': (c_int, [P, P, P, c_int, c_int, c_int, P]),

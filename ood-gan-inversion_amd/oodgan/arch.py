@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer
 from .modules import Generator
 from .synth import generator_channels
 
@@ -216,18 +216,21 @@ class ood_faceGAN_e4e(nn.Module):
         self.ori_lats = lats
         noise = kwargs.get('noise', None)
         offs = kwargs.get('style_offsets', None)        # StyleSpace offsets (B, R) on the generator's styles; the hooks read ``lats``
+        # feature offset (B, C, h, h) on the input of latent ``feature_layer``'s up-conv; a SAMM hook on that latent
+        # receives the raw up-conv output as ever, which now includes the offset's effect
+        fo = dict(feature_offset=kwargs.get('feature_offset', None), feature_layer=kwargs.get('feature_layer', None))
         if self.modulation is None:
-            out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs)
+            out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs, **fo)
             return out, lats
-        out = self._hooked_generate(lats, enc_feats, noise, offs)
+        out = self._hooked_generate(lats, enc_feats, noise, offs, **fo)
         if self.blend_with_gen:
             if self.skip_SA:
-                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs)
+                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs, **fo)
             for _ in range(self.blend_cnt):
                 out = self.blend(x, out, alpha_scale=None)
         return out, lats
 
-    def _hooked_generate(self, lats, enc_feats, noise, style_offsets=None):
+    def _hooked_generate(self, lats, enc_feats, noise, style_offsets=None, feature_offset=None, feature_layer=None):
         """The generator pass with the SAMM hooks (e4e :268-297): fills ``self.aligns`` with the per-level fields; returns G's image."""
         self.feats = [samm.conv1x1(enc_feats[i], self.feats_conv[i].weight, self.feats_conv[i].bias) for i in range(4)]
         self.lats = lats
@@ -236,7 +239,7 @@ class ood_faceGAN_e4e(nn.Module):
         cond_ind = [(2 * (k + 2)) + 1 for k in range(len(conditions))]
         out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, conditions=conditions,
                                 cond_layers=cond_ind, cond_type=self.modulation_type, cond_hook=self._cond_hook,
-                                noise=noise, style_offsets=style_offsets)
+                                noise=noise, style_offsets=style_offsets, feature_offset=feature_offset, feature_layer=feature_layer)
         return out
 
     def blending_mask(self):
@@ -265,7 +268,7 @@ class ood_faceGAN_e4e(nn.Module):
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
-               delta_reg=0.0, style_reg=0.0, pixel_size=None, **kwargs):
+               delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -339,7 +342,16 @@ class ood_faceGAN_e4e(nn.Module):
         (``last_loss_terms['style']``, None when off).  ``edit`` is then a StyleSpace direction, float32 (R,), (1,R) or (B,R), added to delta for
         the final forward only.  ``layer_lr`` scales the step of each layer's style rows.  's' with delta_reg, latent_noise or latent_reg,
         ``style_reg`` without 's', or a W+-shaped edit in 's' raise ValueError; ``use_graph`` with 's' and a zero-padded (narrow) generator
-        NotImplementedError."""
+        NotImplementedError.
+        Feature offset (the F/W+ family: BDInvert, Feature-Style), off by default.  ``feature_layer`` = 3, 5 or 7: beside the
+        latents the loop fits an offset delta (B, C, h, h), from 0, on the 8², 16² or 32² input of the styled up-conv that reads that latent
+        (5: Feature-Style's index) — content no latent can express, a hat or a hand in front of the face, has a code there.  Adam with
+        ``feature_lr`` (None: ``lr``, a choice, not a measured optimum; 0 leaves the offset at zero); ``feature_reg`` = lambda >= 0 adds
+        lambda * mean delta^2 per image (``last_loss_terms['feature']``, None when off).  The final OOD forward runs with the fitted offset;
+        ``self.last_feature_offset`` / ``self.last_feature_layer`` hold it (None without the option) and
+        ``model(x, lats=lats, feature_offset=self.last_feature_offset, feature_layer=self.last_feature_layer)`` reproduces the output.
+        ``edit`` keeps its meaning.  Another index, a layer the generator's size lacks, ``feature_lr`` / ``feature_reg`` without a layer, or
+        latent_space 's' raise ValueError; ``use_graph`` with it and a zero-padded (narrow) generator NotImplementedError."""
         ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
         lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
@@ -351,6 +363,8 @@ class ood_faceGAN_e4e(nn.Module):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         latent_space, layer_lr, delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg, self.generator.n_latent)
         style_reg = check_style_space(latent_space, style_reg, delta_reg, latent_noise, latent_reg)
+        feature_layer, feature_lr, feature_reg = check_feature_offset(feature_layer, feature_lr, feature_reg, lr, latent_space)
+        check_feature_layer(feature_layer, self.generator.n_latent)
         sspace = latent_space == 's'
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
@@ -380,11 +394,16 @@ class ood_faceGAN_e4e(nn.Module):
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
-                            delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size)
+                            delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size, feature_layer=feature_layer, feature_lr=feature_lr,
+                            feature_reg=feature_reg)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
                                latent_anchor=anchor)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
-        kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets')}
+        kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets',
+                                                           'feature_offset')}
+        self.last_feature_offset, self.last_feature_layer = inv.last_feature_offset, (feature_layer if inv.last_feature_offset is not None else None)
+        if self.last_feature_offset is not None:
+            kw.update(feature_offset=self.last_feature_offset, feature_layer=feature_layer)
         if sspace:          # w is the offset on the styles; the latents are the start's
             self.last_refined_lats, self.last_style_offsets = lats0, w
             out, lats = self._ood_forward(x, lats0, enc_feats, noise=noise, style_offsets=w if edit is None else (w + edit).contiguous(), **kw)

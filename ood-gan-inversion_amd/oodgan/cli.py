@@ -57,6 +57,12 @@ Edits and the latent controls of the W+ loop, in the same block
     layer_lr: [f, ...]           one factor >= 0 of ``lr`` per generator layer (18 at 1024²); 0 freezes a layer.  Not with ``latent_space: w``.
     delta_reg: <lambda>          adds lambda * the squared spread of the layers about their mean per image (the symmetric form of e4e's
                                  regulariser, which measures from layer 0).  Default 0 = off.  Not with ``latent_space: w``.
+The feature offset of the W+ loop (the F/W+ family), in the same block:
+
+    feature_layer: 3 | 5 | 7     beside the latents, fit an offset on the 8² / 16² / 32² input of the styled up-conv that reads that latent (5:
+                                 Feature-Style's index): a code for content no latent can express.  Not with ``latent_space: s``.  Default: off.
+    feature_lr: <f>              the offset's learning rate (default: ``lr`` — a choice, not a measured optimum); 0 leaves the offset at zero
+    feature_reg: <lambda>        adds lambda * the mean squared offset per image.  Default 0 = off.
 Where the host work around a chunk runs, in the same block:
 
     io: device | host            device (default): files are uploaded as uint8 and converted on the GPU, the inversion, the mask strip, PSNR and
@@ -81,7 +87,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -179,6 +185,15 @@ def style_options(inv):
     names the option)."""
     return dict(style_reg=check_style_space(inv.get('latent_space', 'w+'), inv.get('style_reg', 0.0), inv.get('delta_reg', 0.0),
                                             inv.get('latent_noise', 0.0), inv.get('latent_reg', 0.0), 'inversion.'))
+
+
+def feature_options(inv, n_latent=None):
+    """``inversion.feature_layer`` / ``feature_lr`` / ``feature_reg`` for ``model.invert``, checked one by one and against
+    ``inversion.latent_space`` (ValueError names the option); ``n_latent``: the generator's latent count once the model exists."""
+    layer, rate, reg = check_feature_offset(inv.get('feature_layer'), inv.get('feature_lr'), inv.get('feature_reg', 0.0), None,
+                                            inv.get('latent_space', 'w+'), 'inversion.')
+    check_feature_layer(layer, n_latent, 'inversion.feature_layer')
+    return dict(feature_layer=layer, feature_lr=rate, feature_reg=reg)
 
 
 def check_edit_space(edit_at, latent_space, has_direction, name=''):
@@ -328,6 +343,7 @@ def run(opts, wplus_steps=None, log=None):
     sched = schedule_options(inv)
     sched.update(latent_options(inv))
     sched.update(style_options(inv))
+    sched.update(feature_options(inv))
     edit_at = edit_option(inv)
     steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     directions_dir = opts.get('directions_dir', './directions')
@@ -353,6 +369,7 @@ def run(opts, wplus_steps=None, log=None):
     check_lpips_size(lpips_size, size, 'inversion.lpips_size')
     pixel_size = check_pixel_size(pixel_size, size, 'inversion.pixel_size')
     latent_options(inv, model.generator.n_latent)
+    feature_options(inv, model.generator.n_latent)
     summary = {}
     for name, dopt in opts['datasets'].items():
         files, direction = load_files_from_path(dopt, directions_dir)

@@ -323,8 +323,17 @@ class GeneratorEngine:
         assert lay == [(L.name, L.lat, L.row, L.cin) for L in self.layers]      # the rows the kernels use
         return lay
 
+    def feature_shape(self, l):
+        """(C, h, h) of the feature offset on the input of the styled up-conv that reads latent ``l``; ValueError for a
+        latent outside FEATURE_LAYERS or one this generator's size does not have, NotImplementedError on a zero-padded generator."""
+        l = check_feature_layer(l, self.n_latent)
+        if self.padded:
+            raise NotImplementedError('feature_layer on a generator whose channel counts are zero-padded to multiples of 16')
+        L = next(L for L in self.layers if L.kind == 'up' and L.lat == l)
+        return (L.cin, L.res // 2, L.res // 2)
+
     def forward(self, latent, noises, save=False, cond_hook=None, cond_layers=None, return_features=False, features_in=None,
-                feature_scale=1.0, range_mode='exact', post_hook=None, style_offsets=None):
+                feature_scale=1.0, range_mode='exact', post_hook=None, style_offsets=None, feature_offset=None, feature_out=None):
         """latent (B,n_latent,S); noises list[num_layers] of (B|1,1,r,r).
         cond_hook(k, raw, latent_i, noise, noise_w) -> cond tensor replacing the raw up-conv output
         (the algebra of OOD_faceGAN_e4e_arch.py:239-242 + model.py:292: layer = cond + w*noise).
@@ -335,7 +344,11 @@ class GeneratorEngine:
         range_mode (split-f16 only, ops.FwdRange): 'exact' measures max|x*s| of every conv input before converting it;
         'carry' (the W+ loop) uses the scales of the previous forward with the fused producers and verifies them.
         style_offsets: float32 (B, R) added to the styles, s = style_affine(latent) + style_offsets (StyleSpace; the columns
-        are those of ``style_layout()``).  Everything downstream reads the sum; the hooks still receive the latent of their layer."""
+        are those of ``style_layout()``).  Everything downstream reads the sum; the hooks still receive the latent of their layer.
+        feature_offset: (l, delta) — float32 (B, C, h, h) added to the input of the styled up-conv that reads latent l, x' = x + delta
+        (F/W+; l in FEATURE_LAYERS, the shape: ``feature_shape(l)``).  ToRGB of the level below and the backward of the conv
+        below keep reading x; with ``save`` both tensors are kept.  Unlike ``features_in`` it leaves carry mode on.  ``feature_out``: the
+        buffer x' is written to (the W+ loop's persistent one); None: a new tensor."""
         if self.padded and (cond_hook is not None or features_in is not None or post_hook is not None):
             raise NotImplementedError('conditioning hooks / feature injection on a generator whose channel counts are zero-padded to multiples of 16')
         if save and (features_in is not None or post_hook is not None):
@@ -343,6 +356,11 @@ class GeneratorEngine:
         if self.padded and style_offsets is not None:
             raise NotImplementedError('style offsets on a generator whose channel counts are zero-padded to multiples of 16')
         B = latent.shape[0]
+        f_lat, f_delta, f_in = None, None, None
+        if feature_offset is not None:
+            f_lat, f_delta = feature_offset
+            if tuple(f_delta.shape) != (B,) + self.feature_shape(f_lat):        # checks the layer too
+                raise ValueError(f'feature_offset for latent {f_lat} must be {(B,) + self.feature_shape(f_lat)}, got {tuple(f_delta.shape)}')
         # forwards are counted: the activations saved for backward() live in pooled scratch buffers (ops.sform_scratch: keyed by shape and
         # stream) and their S-form scales alias the range state — ANY later forward of this engine on the same stream may overwrite them
         self._fwd_serial += 1
@@ -419,6 +437,11 @@ class GeneratorEngine:
                 t = _samm.affine_apply(f, ones * float(feature_scale), zeros)
                 out = _samm.affine_apply(out, ones * float(1.0 - feature_scale), zeros, res=t)
                 pending = None              # an S-form written for the un-mixed tensor is stale
+            if L.lat == f_lat:
+                # the offset layer reads x' = out + delta; ``acts`` keeps the un-offset tensor under the name of the conv that made it.  No
+                # producer below 64² writes an S-form ahead of its reader: what to_s() converts next is x'
+                assert L.kind == 'up' and pending is None and isinstance(out, torch.Tensor), (L.name, pending is not None, type(out))
+                out = f_in = ops.feature_add(out, f_delta, out=feature_out)
             if L.kind == 'conv':
                 if self.sform:
                     # S-form hand-off: style folded in while splitting, the conv then streams its tiles by LDS-DMA
@@ -544,7 +567,7 @@ class GeneratorEngine:
             else:
                 rng.valid = True
         if save:
-            self.saved = dict(acts=acts, s_all=s_all, d_all=d_all, noises=noises, B=B, serial=self._fwd_serial)
+            self.saved = dict(acts=acts, s_all=s_all, d_all=d_all, noises=noises, B=B, serial=self._fwd_serial, f_lat=f_lat, f_in=f_in)
         if return_features:
             feat = out.to_nchw() if isinstance(out, ops.FForm) else out
             return skip, (feat[:, :self.real_channels[self.size]].contiguous() if self.padded else feat)
@@ -566,7 +589,7 @@ class GeneratorEngine:
                     and ops.s2_fuse_supported(B, L.cout, L.cin, 2 * Hd + 1, 2 * Hd + 1))
 
     # ------------------------------------------------------------------ backward (w.r.t. latents only)
-    def backward(self, gimg, grad_scale=1.0, carry_scale=False, wrt='latent'):
+    def backward(self, gimg, grad_scale=1.0, carry_scale=False, wrt='latent', feature_grad=None):
         """gimg (B,3,size,size), already multiplied by ``grad_scale`` -> dL/dlatent (B,n_latent,S).
         ``wrt='styles'``: dL/dstyles (B,R) instead — also the gradient of ``style_offsets`` — still multiplied by ``grad_scale``; the
         contraction with the modulation matrices does not run.
@@ -574,7 +597,10 @@ class GeneratorEngine:
         grad_scale is undone exactly at the end.
         ``carry_scale`` (set by the W+ loop): from the second call on, the activation gradients are produced directly
         in the matrix kernels' input layout with the range scale measured on the previous call (fused producers);
-        the caller must start a new sequence with reset_bwd_state() and check bwd_scale_violated() at its end."""
+        the caller must start a new sequence with reset_bwd_state() and check bwd_scale_violated() at its end.
+        ``feature_grad``: after forward(feature_offset=, save=True), the contiguous float32 buffer of the offset's shape that receives
+        dL/ddelta = dL/dx', still multiplied by ``grad_scale``: the fp32 result of the offset layer's input-gradient conv, which therefore
+        runs without the fused epilogue at that one layer; the gradient continues downward unchanged."""
         from ._lib import lib, check
         import ctypes
         if wrt not in ('latent', 'styles'):
@@ -586,6 +612,12 @@ class GeneratorEngine:
             raise RuntimeError('backward(): another forward of this engine ran after forward(save=True) — the saved activations (pooled S-form / F-form '
                                'buffers, scales of the range state) may have been overwritten; call backward() right after the forward it belongs to')
         acts, s_all, d_all, noises, B = sv['acts'], sv['s_all'], sv['d_all'], sv['noises'], sv['B']
+        f_lat, f_in = sv['f_lat'], sv['f_in']
+        if (feature_grad is not None) != (f_lat is not None):
+            raise RuntimeError('backward(feature_grad=) goes with forward(feature_offset=, save=True), and one needs the other')
+        if feature_grad is not None and not (tuple(feature_grad.shape) == tuple(f_in.shape) and feature_grad.dtype == torch.float32
+                                             and feature_grad.is_contiguous() and feature_grad.device == f_in.device):
+            raise ValueError(f'feature_grad must be a contiguous float32 {tuple(f_in.shape)} tensor on {f_in.device}')
         gs_all = ops.zeros(B, self.R, device=self.device)
         # gradient of the skip chain: gskip[res] for every ToRGB level
         gskip = {self.size: gimg.contiguous()}
@@ -603,6 +635,12 @@ class GeneratorEngine:
                 prev_rgb = L
                 continue
             out, x_in, nz = acts[L.name], acts[L.src], noises[L.noise_idx]
+            # the offset layer: its input was x' = x + delta — the style-gradient dot reads x', the conv writes dL/dx' in fp32 into the
+            # caller's buffer, and the activation backward of the layer below (which reads acts[L.src], the un-offset x) runs unfused
+            at_f = L.lat == f_lat
+            if at_f:
+                x_in = f_in
+            dx_out = feature_grad if at_f else None
             fused_ok = carry_scale and self.fused_bwd and self.bwd_state.get(L.name) is not None
             # last level: out and x_in in F-form -> the activation backward runs inside the input-gradient conv (ops.ActBwdX)
             xf_bwd = (fused_ok and g_feat is None and L.kind == 'conv' and isinstance(out, ops.FForm) and isinstance(x_in, ops.FForm)
@@ -692,7 +730,7 @@ class GeneratorEngine:
                 fz = None
                 Lp = self.by_name.get(L.src)
                 stp = self.bwd_state.get(L.src) if (L.kind == 'up' and Lp is not None and self.fuse_act_bwd) else None
-                if stp is not None and ops.s2_fuse_supported(B, L.cout, L.cin, 2 * Hd + 1, 2 * Hd + 1):
+                if stp is not None and not at_f and ops.s2_fuse_supported(B, L.cout, L.cin, 2 * Hd + 1, 2 * Hd + 1):
                     # the stride-2 conv's result is the gradient w.r.t. the output of the conv layer below (x_in): its
                     # epilogue continues with that layer's activation backward (+ ToRGB branch) and writes the S-form
                     Rp = self.conv_next_rgb[Lp.name]
@@ -709,7 +747,7 @@ class GeneratorEngine:
                     pre = ops.DotActGrad()
                 dx, dot = ops.conv3x3(gin, L.wpk_bwd, L.cin, CONV_S1 if L.kind == 'conv' else CONV_S2, out_scale=s, dotx=x_in,
                                       in_mul2=mul2, dot_into=_Cols(gs_all, L.row, L.cin), jobs=jobs, fuse=fz, want_y=fz is None,
-                                      dot_actgrad=pre)
+                                      dot_actgrad=pre, out=dx_out)
                 fused_in, fused_pre = fz, pre
                 del gin
                 if deferred:
@@ -729,13 +767,13 @@ class GeneratorEngine:
                     # stride-2 conv as stride-1 taps on the four parity images
                     gp = ops.blurT_to_sform_phases(g_pre, self.k4x4_flip, d, mul2,
                                                    out=ops.sform_phases_scratch(B, L.cout, Hd, Hd, self.device))
-                    dx, dot = ops.conv3x3(gp, L.wpk_bwd, L.cin, CONV_S2, out_scale=s, dotx=x_in, in_mul2=mul2)
+                    dx, dot = ops.conv3x3(gp, L.wpk_bwd, L.cin, CONV_S2, out_scale=s, dotx=x_in, in_mul2=mul2, out=dx_out)
                 else:
                     H2 = 2 * Hd + 1
                     P2 = (H2 + 3) // 4 * 4
                     g2 = ops.upfirdn2d(g_pre, self.k4x4_flip, pad=(2, 2), out_pitch=P2)
                     dx, dot = ops.conv3x3(g2, L.wpk_bwd, L.cin, CONV_S2, in_scale=d, out_scale=s, dotx=x_in, in_hw=(H2, H2),
-                                          in_pitch=P2, in_mul2=mul2)
+                                          in_pitch=P2, in_mul2=mul2, out=dx_out)
                     del g2
             if dot is not None:
                 gs_all[:, L.row:L.row + L.cin] += dot
@@ -814,7 +852,7 @@ class _WRun:
     run's constants: seed, image ids, ``steps``) evaluated inside the kernels — a rollback, which restores (w, m, v, t), needs nothing new: a
     repeated window draws the same noise and takes the same learning rates."""
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None):
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -861,10 +899,20 @@ class _WRun:
         self.controls = self.tied or self.layer_lr is not None or self.dl_table is not None
         # ``style_reg`` brings a sixth loss table, mean_r delta_r^2 per step and image
         self.st_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if (self.sspace and inv.style_reg != 0.0) else None
+        # feature offset: a second optimised state beside ``w`` — the offset ``f`` (B, C, h, h) from ``f0`` (zeros), its moments, the
+        # buffer the backward writes dL/dx' into, the buffer x' = x + f is written to and the partial sums of the regulariser, all persistent
+        # and born here, never inside a recorded step (see ``replay`` below); ``feature_reg`` brings a seventh loss table, mean f^2
+        self.f = self.fm = self.fv = self.fg = self.fx = self.fpart = self.ft_table = None
+        if inv.feature_layer is not None:
+            self.f = f0.detach().clone().contiguous()
+            self.fm, self.fv, self.fg, self.fx = (torch.zeros_like(self.f) for _ in range(4))
+            if inv.feature_reg != 0.0:
+                self.ft_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32)
+                self.fpart = ops.feature_step_parts(self.f.shape[0], self.f.numel() // self.f.shape[0], self.f.device)
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
-        self.clean = (0, self.w.clone(), None, None) if self.guard else None     # m = v = 0 at t = 0
+        self.clean = (0, self.w.clone(), None, None, self._fsnap()) if self.guard else None     # m = v = 0 at t = 0
         self.pending, self.exact_until = None, 0
         self.steps_run = 0                                       # forward/backward pairs enqueued, repeated windows included
         self.rollbacks = 0
@@ -901,9 +949,18 @@ class _WRun:
             # W: one vector of noise per image, repeated over the layers — the rows of w_in stay identical
             w_in = ops.latent_noise(self.w, self.dev_t, self.ids, self.steps, inv.latent_noise, inv.noise_ramp, inv.noise_seed, out=self.w_in,
                                     period=self.w.shape[-1] if self.tied else None)
-        img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
-        gimg = self._loss_grad(img)
-        g = eng.backward(gimg, self.gmul, carry_scale=True)
+        if self.f is None:
+            img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
+            gimg = self._loss_grad(img)
+            g = eng.backward(gimg, self.gmul, carry_scale=True)
+        else:
+            # the same step with the offset as a second leaf: its gradient is the dx the backward computes at that layer anyway, its side
+            # of the step one call placed BEFORE the latent-side call, which increments the counter both read
+            img = eng.forward(w_in, self.noises, save=True, range_mode='carry', feature_offset=(inv.feature_layer, self.f), feature_out=self.fx)
+            gimg = self._loss_grad(img)
+            g = eng.backward(gimg, self.gmul, carry_scale=True, feature_grad=self.fg)
+            ops.feature_step(self.f, self.fg, self.fm, self.fv, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown, inv.feature_lr,
+                             inv.betas, inv.eps, grad_div=self.gmul, feature_reg=inv.feature_reg, table=self.ft_table, part=self.fpart)
         if self.lat_table is not None:          # evaluated at w, not at the perturbed w_in
             ops.latent_prior_loss_grad(self.w, self.anchor, g, inv.latent_reg, table=self.lat_table, row_dev=self.dev_t)
         if self.controls:                       # spread term, W tie, per-layer step sizes and Adam: one kernel, the launch count of the Adam call
@@ -972,9 +1029,13 @@ class _WRun:
         if self.inv.on_step is not None:
             self.inv.on_step(self)
 
+    def _fsnap(self):
+        """(f, fm, fv) as they stand, for a snapshot; None without a feature offset."""
+        return None if self.f is None else (self.f.clone(), self.fm.clone(), self.fv.clone())
+
     def _post_check(self):
         eng = self.eng
-        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone())
+        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap())
         ev = torch.cuda.Event()
         ev.record()
         side, done = _flag_stream(self.w.device), torch.cuda.Event()
@@ -997,7 +1058,7 @@ class _WRun:
             self.clean = snap
             return False
         eng = self.eng
-        t0, w, m, v = self.clean
+        t0, w, m, v, fs = self.clean
         self.w.copy_(w)
         if m is None:
             self.m.zero_()
@@ -1005,6 +1066,9 @@ class _WRun:
         else:
             self.m.copy_(m)
             self.v.copy_(v)
+        if fs is not None:                                       # the offset and its moments go back with the latents'
+            for dst, src in zip((self.f, self.fm, self.fv), fs):
+                dst.copy_(src)
         self.t = t0
         self.dev_t.fill_(t0)
         self.rollbacks += 1
@@ -1022,7 +1086,7 @@ class _WRun:
         eng.reset_fwd_state()
         self.exact_until = 0
         self.eager_left = self.warmup
-        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone())
+        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap())
 
     def _advance(self):
         if self.t < self.steps:
@@ -1178,6 +1242,40 @@ def check_style_space(latent_space, style_reg, delta_reg=0.0, latent_noise=0.0, 
     return reg
 
 
+FEATURE_LAYERS = (3, 5, 7)       # the latents whose styled up-conv reads an 8², 16², 32² map (convs.2, convs.4, convs.6); 5: Feature-Style's index
+
+
+def check_feature_layer(value, n_latent=None, name='feature_layer'):
+    """The latent index whose styled up-conv receives the feature offset (None: no offset): ValueError unless it is None or an int (not a
+    bool) in FEATURE_LAYERS and, once the generator is known, one of its ``n_latent`` latents.  From latent 9 on the conv below hands its
+    output to the up-conv only as a fused S-form: there is no fp32 tensor to add to."""
+    if value is None:
+        return None
+    if isinstance(value, bool) or not isinstance(value, int) or value not in FEATURE_LAYERS:
+        raise ValueError(f'{name} must be None or one of {list(FEATURE_LAYERS)}, got {value!r}')
+    if n_latent is not None and value > n_latent - 3:       # the up-convs read latents 1, 3, ..., n_latent - 3; the last latent only a ToRGB
+        raise ValueError(f'{name} {value}: a generator with {n_latent} latents has no styled up-conv that reads it (its image is too small)')
+    return value
+
+
+def check_feature_offset(feature_layer, feature_lr, feature_reg, lr=None, latent_space='w+', prefix=''):
+    """(feature_layer, feature_lr, feature_reg) checked one by one and together.  ``feature_lr`` None: ``lr`` (a choice, not a measured
+    optimum); 0 is allowed and leaves the offset at zero.  Without a layer the other two must be off; latent_space 's' moves the styles of a
+    fixed latent and does not take an offset."""
+    layer = check_feature_layer(feature_layer, None, prefix + 'feature_layer')
+    rate = None if feature_lr is None else check_nonneg(feature_lr, prefix + 'feature_lr')
+    reg = check_nonneg(feature_reg, prefix + 'feature_reg')
+    if layer is None:
+        if rate is not None or reg != 0.0:
+            raise ValueError(f'{prefix}feature_lr / {prefix}feature_reg without {prefix}feature_layer: there is no offset they could act on')
+        return None, None, 0.0
+    if latent_space == 's':
+        raise ValueError(f"{prefix}feature_layer with {prefix}latent_space 's': the feature offset is optimised beside the latents of 'w+' or 'w'")
+    if rate is None:
+        rate = None if lr is None else float(lr)
+    return layer, rate, reg
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1214,6 +1312,13 @@ class WPlusInverter:
     build-defined pull towards styles some w can produce.  ``layer_lr`` applies to the style rows of each layer; the lr ramps apply;
     delta_reg, latent_noise and latent_reg act on latents that do not move and raise ValueError, as ``style_reg`` does outside 's'.
 
+    Feature offset (the F/W+ family: BDInvert, Feature-Style).  ``feature_layer`` = l in FEATURE_LAYERS: beside the latents the
+    loop fits an offset delta (B, C, h, h), from 0, on the input of the styled up-conv that reads latent l, x' = x(w) + delta — at delta = 0
+    the W+ run, and dL/ddelta is the input gradient the backward computes at that layer anyway.  Adam with ``feature_lr`` (None: ``lr``; 0
+    leaves it at zero); ``feature_reg`` = lambda >= 0 adds lambda * mean delta^2 per image (``last_terms['feature']``).  The result is
+    ``last_feature_offset``; the trajectory stays the latents'.  Goes with 'w+' and 'w', every loss term, layer_lr (all zeros: the offset
+    alone is fitted), delta_reg, the schedule and streams; refused with ``use_graph``, latent_space 's' and a zero-padded generator.
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
@@ -1221,7 +1326,7 @@ class WPlusInverter:
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
                  pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
-                 pixel_size=None):
+                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
         # the size the pixel term is taken at: None = the image's own, today's kernels and launch list; an int: the term is the
         # mean of rho over the area-pooled residual (one fused kernel; with ``lpips_size`` of the same value both terms see one view).  A
@@ -1250,6 +1355,12 @@ class WPlusInverter:
         # StyleSpace: ``latent_space='s'`` optimises an offset on the styles; ``style_reg`` * mean_r delta_r^2 per image pulls it
         # back towards styles some w can produce — a term of this build, as delta_reg is
         self.style_reg = check_style_space(self.latent_space, style_reg, self.delta_reg, self.latent_noise, self.latent_reg)
+        # feature offset, off by default: the step is then the launch list above.  ``feature_layer`` in FEATURE_LAYERS: an offset
+        # on the input of that latent's up-conv is fitted beside the latents, by Adam with ``feature_lr`` (None: ``lr`` — a choice, not a
+        # measured optimum; 0 leaves the offset at zero); ``feature_reg`` * mean delta^2 per image keeps it small (``last_terms['feature']``).
+        # After a call ``last_feature_offset`` holds it, (B, C, h, h), None without the option
+        self.feature_layer, self.feature_lr, self.feature_reg = check_feature_offset(feature_layer, feature_lr, feature_reg, lr, self.latent_space)
+        self.last_feature_offset = None
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
@@ -1284,6 +1395,11 @@ class WPlusInverter:
         check_layer_lr(self.layer_lr, int(w0.shape[1]))
         if self.latent_space == 's' and self.engine.padded:
             raise NotImplementedError("latent_space 's' on a generator whose channel counts are zero-padded to multiples of 16")
+        self.last_feature_offset = None
+        fshape = None
+        if self.feature_layer is not None:      # ValueError for a layer this generator lacks, NotImplementedError on a zero-padded one
+            check_feature_layer(self.feature_layer, self.engine.n_latent)
+            fshape = self.engine.feature_shape(self.feature_layer)
         if self.latent_space == 'w':            # the start: the layer mean, on every layer (set-up, not the step)
             w0 = w0.detach().mean(dim=1, keepdim=True).expand_as(w0).contiguous()
         if loss_weight is not None:
@@ -1298,6 +1414,8 @@ class WPlusInverter:
             w = (torch.zeros(B, self.engine.R, device=w0.device, dtype=torch.float32) if self.latent_space == 's'
                  else w0.detach().clone().contiguous())
             empty = torch.empty(0, B, device=w0.device, dtype=torch.float32)
+            if fshape is not None:
+                self.last_feature_offset = torch.zeros((B,) + fshape, device=w0.device, dtype=torch.float32)
             return (w, empty, []) if return_trajectory else (w, empty)
         if return_trajectory:
             streams, use_graph = 1, False
@@ -1309,8 +1427,9 @@ class WPlusInverter:
                     and _lib.lib().oodgan_get_tunable(b's1_big_min_items') == _S1_BIG_DEFAULT)
         if override:
             _lib.set_tunable('s1_big_min_items', MULTI_STREAM_S1_BIG_MIN_ITEMS)
+        f0 = None if fshape is None else ops.zeros(B, *fshape, device=w0.device)
         try:
-            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor)
+            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
@@ -1327,7 +1446,8 @@ class WPlusInverter:
                           'the projector schedule (lr ramps, latent noise, latent prior)'),
                          (self.latent_space != 'w+', f'latent_space {self.latent_space!r}'),
                          (self.layer_lr is not None, 'layer_lr'),
-                         (self.delta_reg != 0.0, 'delta_reg')):
+                         (self.delta_reg != 0.0, 'delta_reg'),
+                         (self.feature_layer is not None, 'feature_layer')):
             if on:
                 raise NotImplementedError(f'use_graph with {what}: use the launch plans (default) instead')
 
@@ -1349,8 +1469,8 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None):
-        """(streams, engines, [(target, w0, noises, beta, ids, anchor)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams).
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams).
         ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
         caller's own."""
         B = w0.shape[0]
@@ -1369,33 +1489,37 @@ class WPlusInverter:
             parts.append((target[sl].contiguous(), w0[sl].detach().contiguous(),
                           [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous(),
                           None if ids is None else ids[sl].contiguous(),
-                          anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor))
+                          anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor,
+                          None if f0 is None else f0[sl].contiguous()))
         if on_side:
             for st in side:
                 st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
         return side, engines, parts
 
     @staticmethod
-    def _gather(side, w, tables):
+    def _gather(side, w, tables, f=None):
         """The per-stream latents (joined along the batch) and loss tables (``tables``: one list per term, None = term off; joined along the
-        images) on the caller's stream; of a single run, its own tensors."""
+        images) on the caller's stream; of a single run, its own tensors.  ``f``: the per-stream feature offsets, joined along the batch
+        like the latents and returned last."""
         cur = torch.cuda.current_stream()
         join = lambda ts, dim: ts[0] if len(ts) == 1 else torch.cat(ts, dim)
         for st in side:
             if st is not None:
                 cur.wait_stream(st)
         out = [join(w, 0)] + [None if ts[0] is None else join(ts, 1) for ts in tables]
-        for ts in [w] + tables:                 # tensors produced on side streams are consumed on the caller's stream
+        if f is not None:
+            out.append(join(f, 0))
+        for ts in [w] + tables + ([] if f is None else [f]):     # tensors produced on side streams are consumed on the caller's stream
             for t in ts:
                 if t is not None:
                     t.record_stream(cur)
         return out
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None):
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None):
         self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
         replay = 'graph' if use_graph else 'plan' if self.use_plan else None
         # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
-        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor)
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0)
         runs = []
         try:
             for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):
@@ -1415,18 +1539,22 @@ class WPlusInverter:
         self.last_stats = {'steps_run': [r.steps_run for r in runs], 'rollbacks': [r.rollbacks for r in runs]}
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
-                                                             [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs]])
+                                                             [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs],
+                                                             [r.ft_table for r in runs]], None if f0 is None else [r.f for r in runs])
+        if f0 is not None:
+            self.last_feature_offset = tables.pop()
         # a graph run has no per-window guard: its flags are read once, here, and a flagged inversion is repeated through the guarded loop
         if use_graph and any(eng.bwd_scale_violated() or eng.fwd_range_violated() for eng in engines):
             return self.invert(target, w0, noises, steps, streams=streams, use_graph=False)
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None):
+    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None):
         self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl,
-                           'style': st}
+                           'style': st, 'feature': ft}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         total = total if lat is None else total + self.latent_reg * lat
         total = total if dl is None else total + self.delta_reg * dl
-        return total if st is None else total + self.style_reg * st
+        total = total if st is None else total + self.style_reg * st
+        return total if ft is None else total + self.feature_reg * ft

@@ -378,6 +378,10 @@ class Generator(nn.Module):
                   features_in=kwargs.get('features_in', None), feature_scale=kwargs.get('feature_scale', 1.0))
         if kwargs.get('style_offsets', None) is not None:       # StyleSpace offsets (B, R), columns as ``style_layout()``; hooks still get the latents
             kw['style_offsets'] = kwargs['style_offsets']
+        if kwargs.get('feature_offset', None) is not None:      # feature offset (B, C, h, h) on the input of latent ``feature_layer``'s up-conv
+            if kwargs.get('feature_layer', None) is None:
+                raise ValueError('feature_offset needs feature_layer, the latent whose up-conv input it is added to')
+            kw['feature_offset'] = (kwargs['feature_layer'], kwargs['feature_offset'])
         # CARRY_FORWARD (opt-in): forward range scales (split-f16 path) carried from the previous forward of this batch size — the W+ loop's scheme
         # (engine.py, ops.FwdRange) for model(x) too: no measurement pass per conv input, the fused producers of the loop.  Scales are powers of two
         # and exact as long as the carried scale keeps the new maximum inside [1, 2^15) — if it does not, the flag is set and the pass
@@ -494,7 +498,7 @@ class StyleGAN2Generator(nn.Module):
 
     def forward(self, styles, input_is_latent=False, input_is_tensor=False, noise=None, randomize_noise=True, truncation=1,
                 truncation_latent=None, inject_index=None, return_latents=False, conditions=None, cond_layers=None,
-                cond_weights=None, cond_type='SFT', style_offsets=None):
+                cond_weights=None, cond_type='SFT', style_offsets=None, feature_offset=None, feature_layer=None):
         if cond_layers is not None and conditions is not None and cond_type == 'NOISE':
             raise NotImplementedError('unknown mod_type NOISE')      # feature_modulation raises the same (stylegan2_arch.py:594)
         # reference quirk (stylegan2_arch.py:555,570): input_is_latent alone skips the MLP *and* the broadcast
@@ -503,4 +507,5 @@ class StyleGAN2Generator(nn.Module):
         return self._inner[0](styles, return_latents=return_latents, inject_index=inject_index, truncation=truncation,
                               truncation_latent=truncation_latent, input_is_latent=input_is_latent,
                               input_is_tensor=input_is_tensor, noise=noise, randomize_noise=randomize_noise,
-                              conditions=conditions, cond_layers=cond_layers, cond_type=cond_type, style_offsets=style_offsets)
+                              conditions=conditions, cond_layers=cond_layers, cond_type=cond_type, style_offsets=style_offsets,
+                              feature_offset=feature_offset, feature_layer=feature_layer)

@@ -1641,3 +1641,59 @@ def style_step(delta, gs, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr
                                        int(total_steps), float(rampup), float(rampdown), float(grad_div), _p(row_lat), _p(layer_lr),
                                        float(style_reg), _p(dst), nrows, _stream()), 'style_step')
     return delta
+
+
+# ---- feature offset of the W+ loop (csrc/feature_offset.hip)
+def feature_add(x, delta, out=None):
+    """x + delta (oodgan_feature_add), both contiguous float32 of one shape: one fp32 addition per element, as a launch of this library (a
+    launch plan replays it).  ``out``: a contiguous float32 tensor of that shape to write into (may be x); None: a new one."""
+    a, d = _dev(x, 'x'), _dev(delta, 'delta')
+    if a.shape != d.shape:
+        raise ValueError(f'feature_add: x {tuple(a.shape)} and delta {tuple(d.shape)} must have one shape')
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.shape == a.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == a.device, \
+        'feature_add: out must be a contiguous float32 tensor of x\'s shape on its device'
+    check(_lib.lib().oodgan_feature_add(_p(a), _p(d), _p(out), a.numel(), _stream()), 'feature_add')
+    return out
+
+
+def feature_step_parts(B, n_per_image, device):
+    """The (B, nparts) float64 buffer ``feature_step`` reduces the regulariser's sums through (oodgan_feature_step_nparts)."""
+    return torch.empty(B, max(1, _lib.lib().oodgan_feature_step_nparts(int(n_per_image))), device=device, dtype=torch.float64)
+
+
+def feature_step(delta, g, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.01, betas=(0.9, 0.999), eps=1e-8, grad_div=1.0,
+                 feature_reg=0.0, table=None, loss_out=None, part=None):
+    """The feature side of a W+ step (oodgan_feature_step): delta, g, m, v (B, ...), all contiguous float32 and updated in place.  ``g`` is
+    dL/dx' times ``grad_div`` (``GeneratorEngine.backward(feature_grad=)``); the step divides it first.  Unlike the latent-side calls this one
+    reads ``t_dev`` and leaves it alone — it uses t = t_dev[0] + 1 and runs BEFORE the latent-side call of the step, which increments.
+    ``feature_reg`` = lambda: g += lambda * dR/ddelta for R_b = mean delta^2; g holds afterwards what Adam consumed.  R goes to row t_dev[0]
+    (clamped) of ``table`` (nrows, B), or to ``loss_out`` (B,); with neither it is not written.  ``part``: the buffer of
+    ``feature_step_parts`` (made here when a table is given without one).  grad_div 1 and nothing on: the bits of ``adam_step_dev_sched``.
+    Returns delta."""
+    a = _dev(delta, 'delta')
+    if a.dim() < 2:
+        raise ValueError(f'feature_step: delta must be (B, ...), got {tuple(a.shape)}')
+    B = a.shape[0]
+    for t, name in ((delta, 'delta'), (g, 'g'), (m, 'm'), (v, 'v')):
+        assert isinstance(t, torch.Tensor) and t.shape == a.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == a.device, \
+            f'feature_step: {name} must be a contiguous float32 tensor of the offset\'s shape on its device (it is updated in place)'
+    assert t_dev.dtype == torch.int32 and t_dev.device == a.device
+    n = a.numel() // B
+    dst, nrows = None, 0
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and table.device == a.device
+        dst, nrows = table, table.shape[0]
+    elif loss_out is not None:
+        assert loss_out.shape == (B,) and loss_out.dtype == torch.float32 and loss_out.is_contiguous() and loss_out.device == a.device
+        dst, nrows = loss_out, 1
+    if dst is not None:
+        if part is None:
+            part = feature_step_parts(B, n, a.device)
+        assert (part.dtype == torch.float64 and part.is_contiguous() and part.device == a.device
+                and part.numel() >= B * _lib.lib().oodgan_feature_step_nparts(n)), 'feature_step: part must be the buffer of feature_step_parts'
+    check(_lib.lib().oodgan_feature_step(_p(delta), _p(g), _p(m), _p(v), B, n, float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                         _p(t_dev), int(total_steps), float(rampup), float(rampdown), float(grad_div), float(feature_reg),
+                                         _p(dst), nrows, _p(part if dst is not None else None), _stream()), 'feature_step')
+    return delta
