@@ -769,6 +769,21 @@ int oodgan_feature_step_nparts(long n_per_image);
 int oodgan_feature_step(float* delta, float* g, float* m, float* v, int B, long n_per_image, float lr, float beta1, float beta2, float eps,
                         const int* t_dev, int total_steps, float rampup, float rampdown, float grad_div, float feature_reg,
                         float* reg_table, int nrows, double* part, void* stream);
+/* P_N+ prior of the W+ loop (csrc/latent_pn.hip; ABI 116; II2S, Zhu et al.: "Improved StyleGAN Embedding: Where are the Good
+ * Latents?" — the reference tree has no such term, it is this build's restatement of the published one).  For w, g (B, L, D), mu (D) and the
+ * symmetric M (D, D) = C diag(1 / sigma^2) C^T of the mapping network's LeakyReLU(5)-ed outputs (oodgan/pn.py), all float32:
+ *   q = l5(w) - mu, l5(t) = t > 0 ? t : 5 t;   loss[b] = (1 / (L D)) sum_l q_bl^T M q_bl;
+ *   g != NULL: g_bl += weight * 2 / (L D) * l5'(w_bl) * (M q_bl), l5'(t) = t > 0 ? 1 : 5 (5 at 0, as torch's leaky_relu backward), ACCUMULATED
+ *   into g (the latent gradient the backward pass returned); g NULL: the loss only, the same bits.
+ * One block per latent row computes M q with every product and sum in double and leaves q . M q in part (B * L doubles, a caller's buffer
+ * that must live until the call has run); one wave per image sums its L partials in a fixed order and rounds once.  No float atomics:
+ * bit-reproducible.  Any D in [1, 4096] and L >= 1; D % 4 == 0 with a 16-byte aligned M reads M 16 bytes per lane, anything else element by
+ * element.  weight < 0 or D > 4096: -1.  Counted by the dispatch counter "pn". */
+int oodgan_pn_prior_fwd_bwd(const float* w, const float* mu, const float* M, float* g, float* loss, int B, int L, int D, float weight,
+                            double* part, void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_pn_prior_fwd_bwd_row(const float* w, const float* mu, const float* M, float* g, float* loss_table, const int* row_dev, int nrows,
+                                int B, int L, int D, float weight, double* part, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 115
+ABI_VERSION = 116
 
 
 class ConvArgs(Structure):
@@ -196,6 +196,8 @@ _SIGS = {
                                     c_int, P, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
+    'oodgan_pn_prior_fwd_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P]),
+    'oodgan_pn_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, P, P]),
     'oodgan_u8_to_input': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'oodgan_tensor2img_u8': (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_double, c_double, P]),
     'oodgan_psnr_ssim_nparts': (c_int, [c_int, c_int, c_int, c_int]),

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
 from .modules import Generator
 from .synth import generator_channels
 
@@ -268,7 +268,8 @@ class ood_faceGAN_e4e(nn.Module):
     def invert(self, x, steps=100, lr=0.01, noise=None, streams=1, use_graph=False, lpips_weight=0.0, lpips_state=None, loss_region='full',
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
-               delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, **kwargs):
+               delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0,
+               pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -351,7 +352,16 @@ class ood_faceGAN_e4e(nn.Module):
         ``self.last_feature_offset`` / ``self.last_feature_layer`` hold it (None without the option) and
         ``model(x, lats=lats, feature_offset=self.last_feature_offset, feature_layer=self.last_feature_layer)`` reproduces the output.
         ``edit`` keeps its meaning.  Another index, a layer the generator's size lacks, ``feature_lr`` / ``feature_reg`` without a layer, or
-        latent_space 's' raise ValueError; ``use_graph`` with it and a zero-padded (narrow) generator NotImplementedError."""
+        latent_space 's' raise ValueError; ``use_graph`` with it and a zero-padded (narrow) generator NotImplementedError.
+        P_N+ prior (II2S, Zhu et al.: "Improved StyleGAN Embedding: Where are the Good Latents?"), off by default.  ``pn_reg`` =
+        lambda >= 0 adds lambda * mean_{l,d} q^T M q per image, q = l5(w) - mu per latent row: l5(t) = t if t > 0 else 5 t undoes the mapping
+        network's last LeakyReLU, and (mu, M) whiten it with the PCA of the mapping network's own outputs — the Mahalanobis distance to the
+        latents the generator was trained on, the control for a fit that reconstructs well and edits badly, where ``latent_reg`` charges every
+        direction of W the same.  The statistics come from ``generator.pn_stats(pn_samples, pn_seed, pn_floor)`` (cached per mapping
+        weights; ``pn_floor``: the relative floor of the variances) unless ``pn_stats``, an ``oodgan.pn.PNStats``, is given: it wins over
+        the three.  ``last_loss_terms['pn']`` is the term's table (None when off), ``self.last_pn_stats`` the statistics used.  A negative or
+        non-finite value, latent_space 's', or statistics of another width, dtype or device raise ValueError; ``use_graph`` with it
+        NotImplementedError."""
         ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
         lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
@@ -365,6 +375,7 @@ class ood_faceGAN_e4e(nn.Module):
         style_reg = check_style_space(latent_space, style_reg, delta_reg, latent_noise, latent_reg)
         feature_layer, feature_lr, feature_reg = check_feature_offset(feature_layer, feature_lr, feature_reg, lr, latent_space)
         check_feature_layer(feature_layer, self.generator.n_latent)
+        pn_reg, pn_samples, pn_seed, pn_floor = check_pn_options(pn_reg, pn_samples, pn_seed, pn_floor, latent_space)
         sspace = latent_space == 's'
         lats0, enc_feats = self.encode(x, **kwargs)
         B = x.shape[0]
@@ -391,13 +402,16 @@ class ood_faceGAN_e4e(nn.Module):
                 anchor = lats0 if anchor == 'start' else (self.avg_latent.reshape(1, -1, self.style_dim) + self.delta_latent)[0].expand(lats0.shape[1:])
             anchor = anchor.detach().float().contiguous()
         sigma0 = latent_noise * self.generator.latent_std() if latent_noise > 0.0 else 0.0
+        if pn_reg > 0.0 and pn_stats is None:
+            pn_stats = self.generator.pn_stats(pn_samples, pn_seed, pn_floor)
+        self.last_pn_stats = pn_stats if pn_reg > 0.0 else None
         inv = WPlusInverter(self.generator.engine(), lr=lr, lpips=lp, lpips_weight=lpips_weight, ssim_weight=ssim_weight, lr_rampup=lr_rampup,
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
                             delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size, feature_layer=feature_layer, feature_lr=feature_lr,
-                            feature_reg=feature_reg)
+                            feature_reg=feature_reg, pn_reg=pn_reg)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
-                               latent_anchor=anchor)
+                               latent_anchor=anchor, pn_stats=pn_stats)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets',
                                                            'feature_offset')}

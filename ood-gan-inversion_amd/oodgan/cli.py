@@ -63,6 +63,15 @@ The feature offset of the W+ loop (the F/W+ family), in the same
                                  Feature-Style's index): a code for content no latent can express.  Not with ``latent_space: s``.  Default: off.
     feature_lr: <f>              the offset's learning rate (default: ``lr`` — a choice, not a measured optimum); 0 leaves the offset at zero
     feature_reg: <lambda>        adds lambda * the mean squared offset per image.  Default 0 = off.
+The P_N+ prior of the W+ loop (II2S, Zhu et al.), in the same block:
+
+    pn_reg: <lambda>             adds lambda * the squared length of the latent in the whitened space of the mapping network's outputs (after
+                                 undoing its last LeakyReLU), the mean over layers and columns, per image: the Mahalanobis distance to the
+                                 latents the generator was trained on — for fits that reconstruct well and edit badly.  Default 0 = off.  Not
+                                 with ``latent_space: s``.  The summary logs each file's final value.
+    pn_samples: <int>            the mapping-network samples the statistics are taken over (default 100000; at least 2, more than 512 without
+                                 a floor); pn_seed: <int> their seed (default 0)
+    pn_floor: <f>                the variances are floored at f * the largest one (default 0: no floor)
 Where the host work around a chunk runs, in the same block:
 
     io: device | host            device (default): files are uploaded as uint8 and converted on the GPU, the inversion, the mask strip, PSNR and
@@ -87,7 +96,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -194,6 +203,14 @@ def feature_options(inv, n_latent=None):
                                             inv.get('latent_space', 'w+'), 'inversion.')
     check_feature_layer(layer, n_latent, 'inversion.feature_layer')
     return dict(feature_layer=layer, feature_lr=rate, feature_reg=reg)
+
+
+def pn_options(inv):
+    """``inversion.pn_reg`` / ``pn_samples`` / ``pn_seed`` / ``pn_floor`` for ``model.invert``, checked one by one and against
+    ``inversion.latent_space`` (ValueError names the option) — before the GPU is touched."""
+    reg, n, seed, floor = check_pn_options(inv.get('pn_reg', 0.0), inv.get('pn_samples', 100000), inv.get('pn_seed', 0), inv.get('pn_floor', 0.0),
+                                           inv.get('latent_space', 'w+'), 'inversion.')
+    return dict(pn_reg=reg, pn_samples=n, pn_seed=seed, pn_floor=floor)
 
 
 def check_edit_space(edit_at, latent_space, has_direction, name=''):
@@ -344,6 +361,7 @@ def run(opts, wplus_steps=None, log=None):
     sched.update(latent_options(inv))
     sched.update(style_options(inv))
     sched.update(feature_options(inv))
+    sched.update(pn_options(inv))
     edit_at = edit_option(inv)
     steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     directions_dir = opts.get('directions_dir', './directions')
@@ -385,7 +403,7 @@ def run(opts, wplus_steps=None, log=None):
                 log.warning('inversion.wplus_steps with an editing direction and inversion.edit: start — the W+ loop fits the UNEDITED input '
                             'starting from edited latents (it works the edit off again); inversion.edit: final applies the direction after the fit')
             model.delta_latent.data += direction.cuda()
-        times, metrics = [], None
+        times, metrics, pn_final = [], None, []
         # ``inversion.batch`` files per call (default 1 = the reference's per-file loop, run_ood_faceGAN_inversion.py:158-182): images are
         # independent on this path, and the W+ loop of one image leaves most of the GPU idle (284 ms per image alone, 131 ms in a batch of 8)
         nb = max(1, int(inv.get('batch', 1)))
@@ -413,6 +431,9 @@ def run(opts, wplus_steps=None, log=None):
                         out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
                                            loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, pixel_size=pixel_size,
                                            noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), edit=edit, **sched)[0]
+                        pn_table = (getattr(model, 'last_loss_terms', None) or {}).get('pn')
+                        if pn_table is not None:        # the last row of the loop's own table: no extra pass
+                            pn_final += [(os.path.basename(f), v) for f, v in zip(chunk, pn_table[-1].tolist())]
                     else:
                         out = (graphed(x) if graphed is not None else model(x))[0]
                     torch.cuda.synchronize()
@@ -434,6 +455,10 @@ def run(opts, wplus_steps=None, log=None):
         log.info('Average wall time per image of %s (files in to files out): %f', name, summary[name]['wall'])
         log.info('Average PSNR of %s: %f', name, summary[name]['psnr'])
         log.info('Average SSIM of %s: %f', name, summary[name]['ssim'])
+        if pn_final:
+            summary[name]['pn'] = dict(pn_final)
+            for f, v in pn_final:
+                log.info('Final P_N+ distance of %s/%s: %f', name, f, v)
         for skipped in ('lpips', 'identity'):
             if (opts.get('metrics') or {}).get(skipped):
                 log.info('%s of %s: skipped (third-party weights not available in this build)', skipped.upper(), name)

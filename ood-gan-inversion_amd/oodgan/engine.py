@@ -852,7 +852,7 @@ class _WRun:
     run's constants: seed, image ids, ``steps``) evaluated inside the kernels — a rollback, which restores (w, m, v, t), needs nothing new: a
     repeated window draws the same noise and takes the same learning rates."""
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None):
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None, pn=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -909,6 +909,11 @@ class _WRun:
             if inv.feature_reg != 0.0:
                 self.ft_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32)
                 self.fpart = ops.feature_step_parts(self.f.shape[0], self.f.numel() // self.f.shape[0], self.f.device)
+        # P_N+ prior: pn_reg * mean_{l,d} q^T M q per image, q = l5(w) - mu, an eighth loss table; the statistics are constant for
+        # the run and shared by the sub-batches, the per-row partial sums a persistent buffer born here, never inside a recorded step
+        self.pn = pn
+        self.pn_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.pn_reg != 0.0 else None
+        self.pn_part = ops.pn_prior_parts(self.w.shape[0], self.w.shape[1], self.w.device) if self.pn_table is not None else None
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
@@ -963,6 +968,8 @@ class _WRun:
                              inv.betas, inv.eps, grad_div=self.gmul, feature_reg=inv.feature_reg, table=self.ft_table, part=self.fpart)
         if self.lat_table is not None:          # evaluated at w, not at the perturbed w_in
             ops.latent_prior_loss_grad(self.w, self.anchor, g, inv.latent_reg, table=self.lat_table, row_dev=self.dev_t)
+        if self.pn_table is not None:           # at the unperturbed w as well; into the true gradient, before the W tie and the step
+            ops.pn_prior_loss_grad(self.w, self.pn.mean, self.pn.matrix, g, inv.pn_reg, table=self.pn_table, row_dev=self.dev_t, part=self.pn_part)
         if self.controls:                       # spread term, W tie, per-layer step sizes and Adam: one kernel, the launch count of the Adam call
             ops.latent_step(self.w, g, self.m, self.v, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown, inv.lr, inv.betas, inv.eps,
                             layer_lr=self.layer_lr, delta_reg=inv.delta_reg, tied=self.tied, table=self.dl_table)
@@ -1276,6 +1283,44 @@ def check_feature_offset(feature_layer, feature_lr, feature_reg, lr=None, latent
     return layer, rate, reg
 
 
+def check_pn(pn_reg, latent_space='w+', pn_stats=None, dim=None, device=None, need_stats=False, prefix=''):
+    """``pn_reg`` as a float, checked against the latent space and, with ``need_stats`` (the call that runs the loop), against the statistics
+    it reads.  ValueError, one place per refusal, naming the option: ``pn_reg`` not a finite number >= 0; ``pn_reg`` > 0 with latent_space 's'
+    (the latents do not move there); ``pn_reg`` > 0 without ``pn_stats``; ``pn_stats`` that is not an ``oodgan.pn.PNStats`` whose ``mean``
+    (dim,) and ``matrix`` (dim, dim) are float32 on ``device``.  With ``pn_reg`` 0 the statistics are not looked at."""
+    reg = check_nonneg(pn_reg, prefix + 'pn_reg')
+    if reg == 0.0:
+        return reg
+    if latent_space == 's':
+        raise ValueError(f"{prefix}pn_reg with {prefix}latent_space 's': the latents stay at their start there, only the style offsets move")
+    if not need_stats:
+        return reg
+    from .pn import PNStats
+    if pn_stats is None:
+        raise ValueError(f'{prefix}pn_reg > 0 needs {prefix}pn_stats: the statistics of the mapping network (Generator.pn_stats)')
+    if not isinstance(pn_stats, PNStats):
+        raise ValueError(f'{prefix}pn_stats must be an oodgan.pn.PNStats, got {type(pn_stats).__name__}')
+    mean, matrix = pn_stats.mean, pn_stats.matrix
+    d = int(mean.numel()) if dim is None else int(dim)
+    if tuple(mean.shape) != (d,) or tuple(matrix.shape) != (d, d):
+        raise ValueError(f'{prefix}pn_stats must hold a ({d},) mean and a ({d}, {d}) matrix for latents of {d} columns, got '
+                         f'{tuple(mean.shape)} and {tuple(matrix.shape)}')
+    if mean.dtype != torch.float32 or matrix.dtype != torch.float32:
+        raise ValueError(f'{prefix}pn_stats must hold float32 tensors, got {mean.dtype} and {matrix.dtype}')
+    if device is not None and (mean.device != torch.device(device) or matrix.device != torch.device(device)):
+        raise ValueError(f'{prefix}pn_stats must be on {device} (PNStats.to), got {mean.device}')
+    return reg
+
+
+def check_pn_options(pn_reg, pn_samples=100000, pn_seed=0, pn_floor=0.0, latent_space='w+', prefix=''):
+    """(pn_reg, pn_samples, pn_seed, pn_floor) checked one by one and against the latent space (``check_pn``): the sample count an int (not a
+    bool) >= 2, the seed an integer in [0, 2^63), the relative floor of the variances a finite number >= 0.  ValueError names the option."""
+    reg = check_pn(pn_reg, latent_space, prefix=prefix)
+    if isinstance(pn_samples, bool) or not isinstance(pn_samples, int) or pn_samples < 2:
+        raise ValueError(f'{prefix}pn_samples must be an int >= 2, got {pn_samples!r}')
+    return reg, pn_samples, check_noise_seed(pn_seed, prefix + 'pn_seed'), check_nonneg(pn_floor, prefix + 'pn_floor')
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1319,6 +1364,12 @@ class WPlusInverter:
     ``last_feature_offset``; the trajectory stays the latents'.  Goes with 'w+' and 'w', every loss term, layer_lr (all zeros: the offset
     alone is fitted), delta_reg, the schedule and streams; refused with ``use_graph``, latent_space 's' and a zero-padded generator.
 
+    P_N+ prior (II2S, Zhu et al.).  ``pn_reg`` = lambda >= 0 adds lambda * mean_{l,d} q^T M q per image, q = l5(w) - mu per latent
+    row, l5 the inverse of the mapping network's last LeakyReLU and (mu, M) the ``oodgan.pn.PNStats`` passed as ``invert(pn_stats=)``
+    (``Generator.pn_stats``): the Mahalanobis distance to the latents the generator was trained on, where ``latent_reg`` charges every
+    direction of W the same.  Evaluated at the unperturbed w, added to the gradient ``backward`` returned (``last_terms['pn']``); goes with
+    'w+' and 'w', every other option and streams; refused with ``use_graph`` (NotImplementedError) and latent_space 's' (ValueError).
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
@@ -1326,7 +1377,7 @@ class WPlusInverter:
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
                  pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
-                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0):
+                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
         # the size the pixel term is taken at: None = the image's own, today's kernels and launch list; an int: the term is the
         # mean of rho over the area-pooled residual (one fused kernel; with ``lpips_size`` of the same value both terms see one view).  A
@@ -1361,6 +1412,9 @@ class WPlusInverter:
         # After a call ``last_feature_offset`` holds it, (B, C, h, h), None without the option
         self.feature_layer, self.feature_lr, self.feature_reg = check_feature_offset(feature_layer, feature_lr, feature_reg, lr, self.latent_space)
         self.last_feature_offset = None
+        # P_N+ prior, off by default: the step is then the launch list above.  ``pn_reg`` = lambda >= 0 adds lambda * the squared
+        # length of l5(w) - mu in the whitened space of the mapping network's outputs, per image; ``invert(pn_stats=)`` brings the statistics
+        self.pn_reg = check_pn(pn_reg, self.latent_space)
         self.last_terms = None
         # launch plans (oodgan_plan_*): on unless OODGAN_USE_PLAN=0; off for a run that returns its trajectory
         self.use_plan = (os.environ.get('OODGAN_USE_PLAN', '1') != '0') if use_plan is None else bool(use_plan)
@@ -1375,7 +1429,7 @@ class WPlusInverter:
         return self._pins[i]
 
     def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None, noise_ids=None,
-               latent_anchor=None):
+               latent_anchor=None, pn_stats=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
         then share the GPU with the matrix kernels of the other instead of running back to back.
@@ -1383,8 +1437,10 @@ class WPlusInverter:
         composite c = target + beta*(G(w) - target); a pixel with beta = 0 has no influence on the run.
         ``noise_ids``: int64 (B,), the id each image draws its latent noise under (default arange(B)); it travels with the image into the
         sub-batches, so an image sees the same noise on one stream or several and in any batch.  ``latent_anchor``: (L,512) or (B,L,512),
-        what ``latent_reg`` pulls towards (required when latent_reg > 0)."""
+        what ``latent_reg`` pulls towards (required when latent_reg > 0).  ``pn_stats``: the ``oodgan.pn.PNStats`` of the mapping network on
+        the latents' device (required when pn_reg > 0; not looked at otherwise)."""
         B = w0.shape[0]
+        pn = pn_stats if check_pn(self.pn_reg, self.latent_space, pn_stats, int(w0.shape[-1]), w0.device, need_stats=True) != 0.0 else None
         size = check_lpips_size(self.lpips_size, int(target.shape[-1]))
         self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
         psize = check_pixel_size(self.pixel_size, int(target.shape[-1]))
@@ -1429,7 +1485,7 @@ class WPlusInverter:
             _lib.set_tunable('s1_big_min_items', MULTI_STREAM_S1_BIG_MIN_ITEMS)
         f0 = None if fshape is None else ops.zeros(B, *fshape, device=w0.device)
         try:
-            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0)
+            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0, pn)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
@@ -1447,7 +1503,8 @@ class WPlusInverter:
                          (self.latent_space != 'w+', f'latent_space {self.latent_space!r}'),
                          (self.layer_lr is not None, 'layer_lr'),
                          (self.delta_reg != 0.0, 'delta_reg'),
-                         (self.feature_layer is not None, 'feature_layer')):
+                         (self.feature_layer is not None, 'feature_layer'),
+                         (self.pn_reg != 0.0, 'pn_reg')):
             if on:
                 raise NotImplementedError(f'use_graph with {what}: use the launch plans (default) instead')
 
@@ -1469,8 +1526,9 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None):
-        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams).
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
+        ``pn``, the read-only statistics of the P_N+ prior, is shared by all of them.
         ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
         caller's own."""
         B = w0.shape[0]
@@ -1490,7 +1548,7 @@ class WPlusInverter:
                           [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous(),
                           None if ids is None else ids[sl].contiguous(),
                           anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor,
-                          None if f0 is None else f0[sl].contiguous()))
+                          None if f0 is None else f0[sl].contiguous(), pn))
         if on_side:
             for st in side:
                 st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
@@ -1515,11 +1573,11 @@ class WPlusInverter:
                     t.record_stream(cur)
         return out
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None):
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None, pn=None):
         self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
         replay = 'graph' if use_graph else 'plan' if self.use_plan else None
         # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
-        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0)
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn)
         runs = []
         try:
             for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):
@@ -1540,7 +1598,7 @@ class WPlusInverter:
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
                                                              [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs],
-                                                             [r.ft_table for r in runs]], None if f0 is None else [r.f for r in runs])
+                                                             [r.ft_table for r in runs], [r.pn_table for r in runs]], None if f0 is None else [r.f for r in runs])
         if f0 is not None:
             self.last_feature_offset = tables.pop()
         # a graph run has no per-window guard: its flags are read once, here, and a flagged inversion is repeated through the guarded loop
@@ -1549,12 +1607,13 @@ class WPlusInverter:
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None):
+    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None):
         self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl,
-                           'style': st, 'feature': ft}
+                           'style': st, 'feature': ft, 'pn': pn}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         total = total if lat is None else total + self.latent_reg * lat
         total = total if dl is None else total + self.delta_reg * dl
         total = total if st is None else total + self.style_reg * st
-        return total if ft is None else total + self.feature_reg * ft
+        total = total if ft is None else total + self.feature_reg * ft
+        return total if pn is None else total + self.pn_reg * pn

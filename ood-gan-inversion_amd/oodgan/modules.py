@@ -304,6 +304,21 @@ class Generator(nn.Module):
             cache[key] = float(((w - w.mean(0, keepdim=True)).double().pow(2).sum() / int(n)).sqrt().item())
         return cache[key]
 
+    @torch.no_grad()
+    def pn_stats(self, n=100000, seed=0, floor=0.0):
+        """The statistics of the P_N+ prior (``oodgan.pn.pn_stats`` states the definition): mean and whitening matrix of
+        l5(style(z)) over ``n`` samples z ~ N(0, I) drawn on the CPU from ``seed`` in chunks of 10000 rows, the mapping network on this
+        module's device, the sums in float64, eigh in float64 on the CPU; ``floor``: the relative floor of the variances.  An
+        ``oodgan.pn.PNStats`` on this module's device, cached per (n, seed, floor) for the mapping weights in use as ``latent_std`` is."""
+        from .pn import pn_stats
+        key = (int(n), int(seed), float(floor), tuple((t.data_ptr(), t._version) for t in self.style.parameters()))
+        cache = self.__dict__.setdefault('_pn_stats', {})
+        if key not in cache:
+            stats = pn_stats(self.style, self.style_dim, self.input.input.device, n, seed, floor)
+            cache.clear()                   # other weights: the old entries can never be hit again
+            cache[key] = stats
+        return cache[key]
+
     def _draw_noises(self, batch, noise, randomize_noise):
         if noise is None:
             if randomize_noise:
@@ -491,6 +506,9 @@ class StyleGAN2Generator(nn.Module):
 
     def latent_std(self, n=10000, seed=0):
         return self._inner[0].latent_std(n, seed)
+
+    def pn_stats(self, n=100000, seed=0, floor=0.0):
+        return self._inner[0].pn_stats(n, seed, floor)
 
     def style_layout(self):
         """``Generator.style_layout``: (module name in the reference generator's layout, latent index, row offset, channels) per style slice."""

@@ -1557,6 +1557,42 @@ def latent_prior_loss_grad(w, anchor, g=None, weight=1.0, loss_out=None, table=N
     return loss
 
 
+# ---- P_N+ prior of the W+ loop (csrc/latent_pn.hip)
+def pn_prior_parts(B, L, device):
+    """The (B, L) float64 buffer ``pn_prior_loss_grad`` leaves each latent row's q . M q in before the per-image sum."""
+    return torch.empty(int(B), int(L), device=device, dtype=torch.float64)
+
+
+def pn_prior_loss_grad(w, mu, M, g=None, weight=1.0, loss_out=None, table=None, row_dev=None, part=None):
+    """The P_N+ prior (oodgan_pn_prior_fwd_bwd): per image mean_{l,d} q^T M q, q = l5(w) - mu per latent row, l5(t) = t if t > 0 else 5 t, for
+    w (B, L, D) (or (B, D): one row per image), ``mu`` (D,) and the symmetric ``M`` (D, D) of ``oodgan.pn.PNStats``, all contiguous float32.
+    ``g`` (w's shape, contiguous): g += weight * 2 / (L D) * l5'(w) * (M q), accumulated into the latent gradient ``backward`` returned;
+    None: forward only, the same loss bits.  ``part``: the buffer of ``pn_prior_parts`` (made here without one; the W+ loop passes its
+    persistent one).  Returns the (B,) values, or None with ``table``; ``loss_out`` / ``table`` + ``row_dev``: as ``mse_loss_grad``."""
+    a, c, m = _dev(w, 'w'), _dev(mu, 'mu'), _dev(M, 'M')
+    if a.dim() not in (2, 3):
+        raise ValueError(f'pn_prior_loss_grad: w must be (B, L, D) or (B, D), got {tuple(a.shape)}')
+    B, D = a.shape[0], a.shape[-1]
+    L = a.shape[1] if a.dim() == 3 else 1
+    if tuple(c.shape) != (D,) or tuple(m.shape) != (D, D):
+        raise ValueError(f'pn_prior_loss_grad: mu must be ({D},) and M ({D}, {D}), got {tuple(c.shape)} and {tuple(m.shape)}')
+    if g is not None:
+        assert g.shape == a.shape and g.dtype == torch.float32 and g.is_contiguous() and g.device == a.device, \
+            'pn_prior_loss_grad: g must be a contiguous float32 tensor of the latent\'s shape (it is updated in place)'
+    if part is None:
+        part = pn_prior_parts(B, L, a.device)
+    assert part.dtype == torch.float64 and part.is_contiguous() and part.device == a.device and part.numel() >= B * L, \
+        'pn_prior_loss_grad: part must be the buffer of pn_prior_parts'
+    lib = _lib.lib()
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    if by_row:
+        check(lib.oodgan_pn_prior_fwd_bwd_row(_p(a), _p(c), _p(m), _p(g), _p(dst), _p(row), nrows, B, L, D, float(weight), _p(part), _stream()),
+              'pn_prior_row')
+    else:
+        check(lib.oodgan_pn_prior_fwd_bwd(_p(a), _p(c), _p(m), _p(g), _p(dst), B, L, D, float(weight), _p(part), _stream()), 'pn_prior')
+    return loss
+
+
 # ---- latent controls of the W+ loop (csrc/wplus_sched.hip, DESIGN.md §18)
 def latent_step(w, g, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.01, betas=(0.9, 0.999), eps=1e-8, layer_lr=None, delta_reg=0.0,
                 tied=False, table=None, loss_out=None):
