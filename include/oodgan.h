@@ -308,7 +308,8 @@ int oodgan_conv3x3(const oodgan_conv_args* args, void* stream);
 
 /* Split-f16 variant (default of the engine): every operand is split v = hi + lo in f16 and each product
  * costs three v_mfma_f32_32x32x16_f16 (hi*hi + hi*lo + lo*hi, fp32 accumulate): fp32-equivalent accuracy
- * (~1e-6 relative) at up to 16/3 the fp32 matrix rate.  Same arguments and epilogues as
+ * (~1e-6 relative: every kernel route is held to 4 x the error of the same formula in float32 on the CPU, against float64, by
+ * tests/test_hip_conv_accuracy.py; DESIGN.md section 2, "accuracy of the conv routes") at up to 16/3 the fp32 matrix rate.  Same arguments and epilogues as
  * oodgan_conv3x3; args->wpk must come from oodgan_pack_conv3x3_f16s, which also writes unscale2[2] =
  * {2^-e, 2^e}: the weights are stored times 2^e (max |w| in [512,1024)) and the kernel multiplies by 2^-e. */
 long oodgan_pack_conv3x3_f16s_bytes(int Co, int Ci, int transpose);

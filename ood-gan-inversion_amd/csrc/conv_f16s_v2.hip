@@ -37,6 +37,16 @@ struct SConv {
     int ys_scale_stride;
 };
 
+// v * out_scale + noise_w * noise + bias in ONE rounding order — fma(noise_w, noise, round(v * out_scale)) + bias, what the aligned-row path
+// below always compiled to — for every path of the epilogue.  Left to the compiler's contraction the ragged-row path and the S-form
+// output fused the other product, fma(v, out_scale, round(noise_w * noise)): `ys` was then the split of a value one fp32 rounding of the
+// epilogue's terms away from the y the same launch returned (relative 2e-3 where the terms cancel; tests/test_hip_conv_accuracy.py).
+__device__ __forceinline__ float epi_affine(float v, float scl, float nw, float nz, float bv) {
+#pragma clang fp contract(off)
+    const float t = v * scl;
+    return __builtin_fmaf(nw, nz, t) + bv;
+}
+
 // Epilogue shared by the S1 and S2 S-form kernels: accumulators -> LDS [channel][256 pixels] -> 16-byte stores of
 // the fp32 NCHW output (fused out-scale / noise / bias / activation, optional style-gradient dot) and, optionally,
 // the S-form of the activated output for the next conv.  All threads of the workgroup must call it.
@@ -110,7 +120,7 @@ __device__ __forceinline__ void tile_epilogue(const KArgs& p, const SConv& sc, f
                     if (yb) {
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            float o = vv[j] * scl + nw * nn[j] + bv;
+                            float o = epi_affine(vv[j], scl, nw, nn[j], bv);
                             if (a.act == OODGAN_ACT_LRELU) o = (o > 0.f ? o : 0.2f * o) * kSqrt2;
                             else if (a.act == OODGAN_ACT_PRELU) o = o > 0.f ? o : sl * o;
                             vv[j] = o;
@@ -154,7 +164,7 @@ __device__ __forceinline__ void tile_epilogue(const KArgs& p, const SConv& sc, f
                         const float nn[4] = {n4.x, n4.y, n4.z, n4.w};
 #pragma unroll
                         for (int j = 0; j < 4; ++j) {
-                            float o = vv[j] * scl + nw * nn[j] + bv;
+                            float o = epi_affine(vv[j], scl, nw, nn[j], bv);
                             if (a.act == OODGAN_ACT_LRELU) o = (o > 0.f ? o : 0.2f * o) * kSqrt2;
                             else if (a.act == OODGAN_ACT_PRELU) o = o > 0.f ? o : sl * o;
                             vv[j] = o;
@@ -167,7 +177,7 @@ __device__ __forceinline__ void tile_epilogue(const KArgs& p, const SConv& sc, f
                         if (px + j >= p.Wout) continue;
                         if (db) dsum += vv[j] * db[(long)m * HWo + pix + j];
                         if (yp) {
-                            float o = vv[j] * scl + (nzp ? nw * nzp[pix + j] : 0.f) + bv;
+                            float o = epi_affine(vv[j], scl, nw, nzp ? nzp[pix + j] : 0.f, bv);
                             if (a.act == OODGAN_ACT_LRELU) o = (o > 0.f ? o : 0.2f * o) * kSqrt2;
                             else if (a.act == OODGAN_ACT_PRELU) o = o > 0.f ? o : sl * o;
                             yp[j] = o;
@@ -203,14 +213,14 @@ __device__ __forceinline__ void tile_epilogue(const KArgs& p, const SConv& sc, f
                 c_slp[j] = *((a.act == OODGAN_ACT_PRELU && a.slope) ? a.slope + mc : dmy);
                 c_ysc[j] = *(ysc ? ysc + mc : dmy);
             }
-            const float nz = nzp ? nw * nzr : 0.f;
+            const float nz = nzp ? nzr : 0.f;
             half8 hv[2], lv[2];
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
                 const int ml = g16 * 16 + j, m = m0 + ml;
                 float o = 0.f;
                 if (m < a.M) {
-                    o = lo[ml * OP + pxl] * (osc ? c_osc[j] : 1.f) + nz + (a.bias ? c_bia[j] : 0.f);
+                    o = epi_affine(lo[ml * OP + pxl], osc ? c_osc[j] : 1.f, nw, nz, a.bias ? c_bia[j] : 0.f);
                     if (a.act == OODGAN_ACT_LRELU) o = (o > 0.f ? o : 0.2f * o) * kSqrt2;
                     else if (a.act == OODGAN_ACT_PRELU) o = o > 0.f ? o : c_slp[j] * o;
                     if (ysc) o *= c_ysc[j];
