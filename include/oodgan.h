@@ -60,7 +60,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) and "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) and "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);
@@ -683,6 +683,27 @@ int oodgan_pooled_pixel_loss_fwd_bwd_row(const float* img, const float* target, 
                                          float* comp, float* part, float* loss_table, const int* row_dev, int nrows, int B, int C, int H,
                                          int W, int f, int kind, float scale, int wrt_gen, float grad_mul, void* stream);
 int oodgan_pooled_pixel_loss_nparts(long CHWs, int f);
+/* The pixel term on an antialiased resampled view (the W+ loop's pixel_filter): D(G) = Ay · G · Ax^T per plane.  F in
+ * {2, 4, 8, 16}, Hs = H/F, Ws = W/F; a filter of support s in {2, 4, 6} has T = s*F taps per output; Ay (Hs,T) and Ax (Ws,T) are float32 tap
+ * tables: output q reads inputs F*q - (T-F)/2 + j with weight A[q][j], j = 0 .. T-1.  A tap outside the plane must have weight 0 (the
+ * kernels clamp its index and never read out of bounds), so a window may be wider than the image.  oodgan_resample_fwd writes the view
+ * `out` (BC,Hs,Ws) of img (BC,H,W).  The loss: r = D(img) - target_view (B,C,Hs,Ws), loss[b] = mean over C*Hs*Ws of rho(r), kind 0 = the
+ * square, else an OODGAN_ROBUST_* kind at `scale` (rho, psi as oodgan_robust_loss_fwd_bwd).  Kernel one writes psi(r) to r_scratch
+ * (B,C,Hs,Ws; psi = r for the square) and one partial of rho per tile to part (B, oodgan_resampled_pixel_loss_nparts(C, H, W, F)); the
+ * partials are reduced as in the other pixel terms.  Kernel two writes the true gradient gimg (B,C,H,W) = gs * Ay^T psi(r) Ax, gs =
+ * grad_mul/(C*Hs*Ws) (twice that for the square): a gather over the at most s pooled positions per axis that read a pixel.  gimg NULL:
+ * forward only, the same loss bit for bit.  No float atomics, fixed summation order: bit-reproducible.  OODGAN_E_ARG with a message,
+ * nothing launched, for another F or s, a plane that is no multiple of F, null tables or pointers, an unknown kind, a bad scale and
+ * B*C <= 0.  Accepted loss calls are counted by the dispatch counter "resampled_pixel". */
+int oodgan_resample_fwd(const float* img, const float* Ay, const float* Ax, float* out, int BC, int H, int W, int F, int s, void* stream);
+int oodgan_resampled_pixel_loss_fwd_bwd(const float* img, const float* target_view, const float* Ay, const float* Ax, float* gimg,
+                                        float* r_scratch, float* part, float* loss, int B, int C, int H, int W, int F, int s, int kind,
+                                        float scale, float grad_mul, void* stream);
+/* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
+int oodgan_resampled_pixel_loss_fwd_bwd_row(const float* img, const float* target_view, const float* Ay, const float* Ax, float* gimg,
+                                            float* r_scratch, float* part, float* loss_table, const int* row_dev, int nrows, int B, int C,
+                                            int H, int W, int F, int s, int kind, float scale, float grad_mul, void* stream);
+int oodgan_resampled_pixel_loss_nparts(int C, int H, int W, int F);
 /* torch.optim.Adam step (no weight decay, no amsgrad), step index t>=1 given by the host:
  * anchors: get_optimizer (src/models/OOD_faceGAN_model.py:398-400). */
 int oodgan_adam_step(float* w, const float* g, float* m, float* v, long n, float lr, float beta1,

@@ -56,7 +56,9 @@ enum { OODGAN_DC_STRIPX = 0, OODGAN_DC_STRIP, OODGAN_DC_S1BIG, OODGAN_DC_S1V2, O
        // calls of the pooled pixel-term kernel (loss_pixel.hip, oodgan_pooled_pixel_loss_fwd_bwd[_row])
        OODGAN_DC_POOLED_PIXEL,
        // calls of the P_N+ prior (latent_pn.hip, oodgan_pn_prior_fwd_bwd[_row])
-       OODGAN_DC_PN, OODGAN_DC_COUNT };
+       OODGAN_DC_PN,
+       // calls of the resampled pixel term (loss_resample.hip, oodgan_resampled_pixel_loss_fwd_bwd[_row])
+       OODGAN_DC_RESAMPLED_PIXEL, OODGAN_DC_COUNT };
 void count_dispatch(int id);
 
 // One process per GPU: per-kernel setup (dynamic-LDS attributes, the zero page and CU count of the F-form strip

@@ -28,6 +28,31 @@ __global__ __launch_bounds__(64) void mean_finish_kernel(const T* __restrict__ p
     if (lane == 0) loss[row + b] = s * inv_n;
 }
 
+// ---- rho and psi of the pixel terms (loss_pixel.hip; loss_resample.hip)
+// the square next to the public OODGAN_ROBUST_* kinds (1..3); it has no scale
+constexpr int kSquare = 0;
+
+// rho(d) (returned) and psi(d) of one element; s2 is a normal float (the robust entry points check it), so no denominator is zero
+template <int KIND>
+__device__ __forceinline__ float rho_psi(float d, float s, float s2, float& psi) {
+    if constexpr (KIND == kSquare) {
+        psi = d;
+        return d * d;
+    } else if constexpr (KIND == OODGAN_ROBUST_CHARBONNIER) {
+        const float q = sqrtf(d * d + s2);
+        psi = d / q;
+        return q;
+    } else if constexpr (KIND == OODGAN_ROBUST_HUBER) {
+        const float a = fabsf(d);
+        psi = fminf(fmaxf(d, -s), s);
+        return a <= s ? 0.5f * d * d : s * (a - 0.5f * s);
+    } else {
+        const float r = s2 / (d * d + s2);
+        psi = d * r * r;
+        return 0.5f * d * d * r;
+    }
+}
+
 // ---- F x F windows of the area pool (loss_pool.hip) and of the pooled pixel term (loss_pixel.hip): one thread owns a window
 template <int F>
 struct Row {                                     // the vector a window row is read in, and how many of them a row has

@@ -17,29 +17,7 @@ using namespace oodgan;
 
 namespace {
 
-// the square next to the public OODGAN_ROBUST_* kinds (1..3); it has no scale
-constexpr int kSquare = 0;
-
-// rho(d) (returned) and psi(d) of one element; s2 is a normal float (the robust entry points check it), so no denominator is zero
-template <int KIND>
-__device__ __forceinline__ float rho_psi(float d, float s, float s2, float& psi) {
-    if constexpr (KIND == kSquare) {
-        psi = d;
-        return d * d;
-    } else if constexpr (KIND == OODGAN_ROBUST_CHARBONNIER) {
-        const float q = sqrtf(d * d + s2);
-        psi = d / q;
-        return q;
-    } else if constexpr (KIND == OODGAN_ROBUST_HUBER) {
-        const float a = fabsf(d);
-        psi = fminf(fmaxf(d, -s), s);
-        return a <= s ? 0.5f * d * d : s * (a - 0.5f * s);
-    } else {
-        const float r = s2 / (d * d + s2);
-        psi = d * r * r;
-        return 0.5f * d * d * r;
-    }
-}
+// kSquare, rho_psi<KIND>: loss_common.hpp (the resampled pixel term of loss_resample.hip applies the same rho and psi)
 
 // one float4 of the walk: the sum of its four rho, x to w; gradient and composite as asked for.
 // w: the loss weights of the four pixels (BETA) — gscale * 1 == gscale, so beta == 1 stores what the plain form stores

@@ -181,6 +181,11 @@ _SIGS = {
     'oodgan_pooled_pixel_loss_fwd_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float, P]),
     'oodgan_pooled_pixel_loss_fwd_bwd_row': (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
                                                      c_float, P]),
+    'oodgan_resample_fwd': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, P]),
+    'oodgan_resampled_pixel_loss_nparts': (c_int, [c_int, c_int, c_int, c_int]),
+    'oodgan_resampled_pixel_loss_fwd_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P]),
+    'oodgan_resampled_pixel_loss_fwd_bwd_row': (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                                                        c_float, P]),
     'oodgan_adam_step': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, c_int, P]),
     'oodgan_adam_step_dev': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, P]),
     'oodgan_adam_step_dev_sched': (c_int, [P, P, P, P, c_long, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, P]),
@@ -252,7 +257,7 @@ def set_tunable(name, value):
 
 
 def dispatch_count(name):
-    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", the area-pool kernels, "area_pool", or the pooled pixel-term kernel, "pooled_pixel") since load /
+    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", the area-pool kernels, "area_pool", the pooled pixel-term kernel, "pooled_pixel", or the resampled pixel term, "resampled_pixel") since load /
     dispatch_reset() (include/oodgan.h)."""
     n = lib().oodgan_dispatch_count(name.encode())
     if n < 0:

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
 from .modules import Generator
 from .synth import generator_channels
 
@@ -269,7 +269,7 @@ class ood_faceGAN_e4e(nn.Module):
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
                delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0,
-               pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, **kwargs):
+               pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, pixel_filter=None, pixel_target=None, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -361,7 +361,16 @@ class ood_faceGAN_e4e(nn.Module):
         weights; ``pn_floor``: the relative floor of the variances) unless ``pn_stats``, an ``oodgan.pn.PNStats``, is given: it wins over
         the three.  ``last_loss_terms['pn']`` is the term's table (None when off), ``self.last_pn_stats`` the statistics used.  A negative or
         non-finite value, latent_space 's', or statistics of another width, dtype or device raise ValueError; ``use_graph`` with it
-        NotImplementedError."""
+        NotImplementedError.
+        ``pixel_filter``: the filter of the ``pixel_size`` view.  None or 'box' (default): the area pool above, unchanged.
+        'bilinear', 'bicubic' (Keys, a = -0.5) or 'lanczos3': the antialiased resize D that ``F.interpolate(antialias=True)``, PIL and the
+        thumbnailers apply, the operator a real low-resolution photograph was made with; the term is the mean of rho over D(G) - D(x) and its
+        gradient the true adjoint, two HIP kernels, one launch more per step.  ``pixel_target``: a float32 (B,3,n,n) image in [-1, 1] on the
+        model's device, the low-resolution photograph at its own size: it replaces D(x) (with 'box': the pooled target) and fixes
+        ``pixel_size`` = n.  ``x`` stays the full-size input of the encoder, the OOD forward and the blend, and LPIPS and SSIM, if on, keep
+        comparing with ``x``.  A filter without a ``pixel_size`` below the image size, an unknown filter, a ``pixel_size`` that differs from
+        the target's size, a size / n outside {2, 4, 8, 16}, or either option with ``loss_region`` other than 'full' raise ValueError;
+        ``use_graph`` with them NotImplementedError."""
         ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
         lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
@@ -369,6 +378,13 @@ class ood_faceGAN_e4e(nn.Module):
         pixel_loss, pixel_scale = check_pixel_loss(pixel_loss, pixel_scale)
         lpips_size = check_lpips_size(lpips_size, int(x.shape[-1]))
         pixel_size = check_pixel_size(pixel_size, int(x.shape[-1]))
+        pixel_filter = check_pixel_filter(pixel_filter)
+        pixel_target, pixel_size = check_pixel_target(pixel_target, x, pixel_size)
+        pixel_size = check_pixel_size(pixel_size, int(x.shape[-1]), 'pixel_size' if pixel_target is None else 'the size of pixel_target')
+        if pixel_filter is not None and pixel_size is None:
+            raise ValueError(f'pixel_filter {pixel_filter!r} needs pixel_size (or pixel_target) below the image size')
+        if (pixel_filter is not None or pixel_target is not None) and not (isinstance(loss_region, str) and loss_region == 'full'):
+            raise ValueError("pixel_filter / pixel_target take loss_region='full' only: the masked objective is taken on the area-pooled view of x")
         if not isinstance(latent_anchor, torch.Tensor) and latent_anchor not in ('start', 'mean'):
             raise ValueError(f"latent_anchor must be 'start', 'mean' or a tensor, got {latent_anchor!r}")
         latent_space, layer_lr, delta_reg = check_latent_controls(latent_space, layer_lr, delta_reg, self.generator.n_latent)
@@ -409,9 +425,9 @@ class ood_faceGAN_e4e(nn.Module):
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
                             delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size, feature_layer=feature_layer, feature_lr=feature_lr,
-                            feature_reg=feature_reg, pn_reg=pn_reg)
+                            feature_reg=feature_reg, pn_reg=pn_reg, pixel_filter=pixel_filter)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
-                               latent_anchor=anchor, pn_stats=pn_stats)
+                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target)
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets',
                                                            'feature_offset')}

@@ -34,6 +34,14 @@ Where the W+ loss looks, in the same block:
                                  and target, one fused kernel.  Absent (default) or the generator size: the full-resolution term.  It must divide
                                  the generator size by 1, 2, 4, 8 or 16; anything else is an error.  For a low-resolution photograph: feed it
                                  nearest-upsampled and give its own size here.
+    pixel_filter: <name>         the filter of the ``pixel_size`` view: box (default: the area pool), bilinear, bicubic or lanczos3 —
+                                 the antialiased resize a real low-resolution photograph was made with (PIL, OpenCV, F.interpolate(antialias=True)).
+                                 Needs ``pixel_size`` or ``pixel_target``; not with ``loss_region: blend`` or ``mask_dir``.
+    pixel_target: file           an input file of side n with generator size / n in 2, 4, 8, 16 supplies its own pixels as the target of the pixel
+                                 term (the same uint8 -> [-1, 1] RGB conversion as the input, no resize) and fixes ``pixel_size`` = n; the
+                                 bilinearly enlarged image still feeds the encoder and the OOD forward.  The files of one batch must share one
+                                 size; a file already at the generator size is an error.  Absent (default): the target's view is made from the
+                                 enlarged input.
 The projector schedule of the W+ loop (rosinality's projector.py), in the same block, everything off by default:
 
     lr_rampup, lr_rampdown: <f>  fractions of the run over which the learning rate ramps up linearly / follows a cosine down (projector: 0.05, 0.25)
@@ -96,7 +104,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -169,6 +177,31 @@ def evaluate(gt_bgr, res_bgr, metrics, opt):
         metrics['ssim'].append(imgio.calculate_ssim(gt_bgr, res_bgr, crop_border=opt['ssim']['crop_border'],
                                                     test_y_channel=opt['ssim']['test_y_channel']))
     return metrics
+
+
+def pixel_target_option(inv):
+    """``inversion.pixel_target``: absent / None (the view of the enlarged input) or 'file' (each input file's own pixels); returns True for 'file'."""
+    v = inv.get('pixel_target')
+    if v is not None and v != 'file':
+        raise ValueError(f"inversion.pixel_target must be absent or 'file', got {v!r}")
+    return v == 'file'
+
+
+def pixel_target_from_files(bgrs, files, size):
+    """The pixel target of one batch under ``inversion.pixel_target: file``: the files' own pixels, (B,3,n,n) float32 RGB in [-1, 1] on the
+    device, converted as the input is and never resized.  ``bgrs``: the decoded files, (n,n,3) uint8 tensors on the device or host arrays
+    (any dtype holding 0..255).  ValueError for files of different sizes, a file that is not square, one already at the generator size and
+    a side n with size / n not in 2, 4, 8, 16."""
+    shapes = {tuple(b.shape[:2]) for b in bgrs}
+    if len(shapes) != 1:
+        raise ValueError(f'inversion.pixel_target: file needs the files of one batch at one size, got {sorted(shapes)} for {list(files)}')
+    h, n = next(iter(shapes))
+    if h != n or n >= size or size % n != 0 or size // n not in (2, 4, 8, 16):
+        raise ValueError(f'inversion.pixel_target: file needs square inputs of side n with {size} / n in [2, 4, 8, 16], got {h}x{n} for '
+                         f'{list(files)}' + (' (already at the generator size: drop the option)' if (h, n) == (size, size) else ''))
+    if isinstance(bgrs[0], torch.Tensor):
+        return imgio.input_from_u8(torch.stack(bgrs), n)
+    return torch.cat([imgio.image_to_input(bgr, n, device='cuda') for bgr in bgrs], 0)
 
 
 def schedule_options(inv):
@@ -357,6 +390,12 @@ def run(opts, wplus_steps=None, log=None):
     out_size = (opts.get('network_g') or {}).get('out_size')
     lpips_size = check_lpips_size(inv.get('lpips_size'), out_size if isinstance(out_size, int) else None, 'inversion.lpips_size')
     pixel_size = check_pixel_size(inv.get('pixel_size'), out_size if isinstance(out_size, int) else None, 'inversion.pixel_size')
+    pixel_filter = check_pixel_filter(inv.get('pixel_filter'), 'inversion.pixel_filter')
+    target_from_file = pixel_target_option(inv)
+    if (pixel_filter is not None or target_from_file) and (mask_dir or loss_region != 'full'):
+        raise ValueError('inversion.pixel_filter / inversion.pixel_target take neither inversion.mask_dir nor inversion.loss_region: blend')
+    if pixel_filter is not None and pixel_size is None and not target_from_file:
+        raise ValueError(f'inversion.pixel_filter: {pixel_filter} needs inversion.pixel_size or inversion.pixel_target: file')
     sched = schedule_options(inv)
     sched.update(latent_options(inv))
     sched.update(style_options(inv))
@@ -386,6 +425,8 @@ def run(opts, wplus_steps=None, log=None):
     size = model.generator.size
     check_lpips_size(lpips_size, size, 'inversion.lpips_size')
     pixel_size = check_pixel_size(pixel_size, size, 'inversion.pixel_size')
+    if pixel_filter is not None and pixel_size is None and not target_from_file:
+        raise ValueError(f'inversion.pixel_filter: {pixel_filter} needs inversion.pixel_size below the generator size {size}')
     latent_options(inv, model.generator.n_latent)
     feature_options(inv, model.generator.n_latent)
     summary = {}
@@ -425,11 +466,13 @@ def run(opts, wplus_steps=None, log=None):
                     bgrs = [imgio.imread(f).astype(np.float64) for f in chunk]
                     x = torch.cat([imgio.image_to_input(bgr, size, device='cuda') for bgr in bgrs], 0)
                 region = load_loss_weights(chunk, mask_dir, size).cuda() if (mask_dir and steps > 0) else loss_region
+                pixel_target = pixel_target_from_files(bgrs, chunk, size) if (target_from_file and steps > 0) else None
                 with torch.no_grad():
                     t0 = time.time()
                     if steps > 0:
                         out = model.invert(x, steps=steps, lr=lr, streams=streams, lpips_weight=lpips_weight, lpips_state=lpips_state,
                                            loss_region=region, ssim_weight=ssim_weight, pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, pixel_size=pixel_size,
+                                           pixel_filter=pixel_filter, pixel_target=pixel_target,
                                            noise_ids=torch.arange(c0, c0 + len(chunk), dtype=torch.int64, device='cuda'), edit=edit, **sched)[0]
                         pn_table = (getattr(model, 'last_loss_terms', None) or {}).get('pn')
                         if pn_table is not None:        # the last row of the loop's own table: no extra pass

@@ -852,7 +852,8 @@ class _WRun:
     run's constants: seed, image ids, ``steps``) evaluated inside the kernels — a rollback, which restores (w, m, v, t), needs nothing new: a
     repeated window draws the same noise and takes the same learning rates."""
 
-    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None, pn=None):
+    def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None, pn=None,
+                 px=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -880,7 +881,15 @@ class _WRun:
         # ``target`` and ``lp_target``, made here, once: never born inside a recorded step (see ``replay`` below), and the step reads it
         # instead of the full target — with a loss weight the kernel pools beta*(G - x) from the full target and this stays None
         self.px_f = inv._pixel_f
-        self.px_target = ops.area_pool(target.contiguous(), self.px_f) if (self.px_f > 1 and beta is None) else None
+        self.px_target = ops.area_pool(target.contiguous(), self.px_f) if (self.px_f > 1 and beta is None and px is None) else px
+        # ``pixel_filter``: the view is the antialiased resize Ay · G · Ax^T instead of the area pool.  The two tap tables and
+        # the target's view — the resized target, or the caller's own low-resolution ``pixel_target`` (``px``) — are persistent inputs too
+        self.px_tables = None
+        if inv.pixel_filter is not None:
+            H, W = int(target.shape[-2]), int(target.shape[-1])
+            self.px_tables = (ops.resample_tables(inv.pixel_filter, H, self.px_f).to(target.device),
+                              ops.resample_tables(inv.pixel_filter, W, self.px_f).to(target.device))
+            self.px_target = px if px is not None else ops.resample_view(target.contiguous(), *self.px_tables, self.px_f)
         # optional SSIM term (csrc/loss_ssim.hip): a third loss table, 1 - SSIM per step and image
         self.ss_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.ssim_weight != 0.0 else None
         # projector schedule (csrc/wplus_sched.hip).  ``w_in``, the perturbed latent the generator reads, is a persistent
@@ -984,11 +993,13 @@ class _WRun:
         lambda * gmul * their part; with ``lpips_size`` LPIPS is taken on the area-pooled view of the same image.  With a loss weight beta
         the terms are taken on the composite c: alone, the composite MSE writes beta*dL/dc in one kernel; with LPIPS or
         SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards.  With ``pixel_size`` the pixel term is the fused
-        kernel of the pooled view: the same call, the same number of launches, a full-resolution gradient and composite."""
+        kernel of the pooled view: the same call, the same number of launches, a full-resolution gradient and composite; with
+        ``pixel_filter`` the kernel pair of the antialiased view: the same call again, one launch more."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
         on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
         _, gimg, c = ops.pixel_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if on_c else 'gen',
-                                         composite=on_c, table=self.lbuf, row_dev=row, pool=self.px_f, target_pooled=self.px_target)
+                                         composite=on_c, table=self.lbuf, row_dev=row, pool=self.px_f, target_pooled=self.px_target,
+                                         resample=self.px_tables)
         x = c if on_c else img
         if self.lp is not None and self.lp_f == 1:
             self.lp.loss_and_grad(x, gimg, inv.lpips_weight * gmul, table=self.lp_table, row_dev=row, target_taps=self.lp_target)
@@ -1179,6 +1190,36 @@ def check_pixel_size(value, image_size=None, name='pixel_size'):
     return value
 
 
+PIXEL_FILTERS = ('box',) + tuple(ops.RESAMPLE_FILTERS)
+
+
+def check_pixel_filter(value, name='pixel_filter'):
+    """The filter of the view the pixel term is taken on with ``pixel_size``: ValueError unless it is None or one of
+    PIXEL_FILTERS.  Returns None for None and 'box' (the area pool of §20: today's path), else the name."""
+    if value is None or (isinstance(value, str) and value == 'box'):
+        return None
+    if not isinstance(value, str) or value not in PIXEL_FILTERS:
+        raise ValueError(f'{name} must be None or one of {list(PIXEL_FILTERS)}, got {value!r}')
+    return value
+
+
+def check_pixel_target(value, target, pixel_size, name='pixel_target'):
+    """``pixel_target``, the caller's own low-resolution target of the pixel term: ValueError unless it is None or a float32 (B,C,n,n*W/H)
+    tensor on the target's device with H / n in PIXEL_POOL_FACTORS above 1; it fixes ``pixel_size`` = n, so a ``pixel_size`` that differs is
+    an error.  Returns (the tensor, contiguous, or None; the pixel_size in force)."""
+    if value is None:
+        return None, pixel_size
+    B, C, H, W = target.shape
+    if not isinstance(value, torch.Tensor) or value.dtype != torch.float32 or value.dim() != 4 or value.device != target.device:
+        raise ValueError(f'{name} must be a float32 (B,C,n,n) tensor on {target.device}')
+    n, m = int(value.shape[-2]), int(value.shape[-1])
+    if tuple(value.shape[:2]) != (B, C) or n < 1 or H % n != 0 or H // n not in PIXEL_POOL_FACTORS[1:] or m * (H // n) != W:
+        raise ValueError(f'{name} must have shape ({B}, {C}, n, n) with {H} / n in {list(PIXEL_POOL_FACTORS[1:])}, got {tuple(value.shape)}')
+    if pixel_size is not None and pixel_size != m:
+        raise ValueError(f'{name} of size {m} fixes pixel_size = {m}, got pixel_size {pixel_size!r}')
+    return value.contiguous(), m
+
+
 PIXEL_LOSSES = ('mse',) + tuple(ops.ROBUST_KINDS)
 
 
@@ -1334,7 +1375,7 @@ class WPlusInverter:
     ``noise=<list>`` (model.py:483-585), torch.optim.Adam as built by get_optimizer
     (src/models/OOD_faceGAN_model.py:398-400), basicsr MSELoss (losses.py:58-83).
 
-    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight; with ``pixel_size`` on the view area-pooled to that size) — + lpips_weight * LPIPS
+    The loss of a step is defined once, in ``_WRun._loss_grad``: the pixel term — MSE, or the robust ``pixel_loss`` (on the composite with a loss weight; with ``pixel_size`` on the view area-pooled to that size or, with ``pixel_filter``, resized to it by that antialiased filter) — + lpips_weight * LPIPS
     (with ``lpips_size`` on the image and the target area-pooled to that size) + ssim_weight * (1 - SSIM); the step index is a device counter in every mode.
     The step itself is defined once too, ``_WRun._eager_step``: run from Python, replayed from a launch plan (default) or, with
     ``invert(use_graph=True)``, from a captured hipGraph, with a trajectory or without, on any number of streams.
@@ -1377,8 +1418,12 @@ class WPlusInverter:
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
                  pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
-                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0):
+                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0, pixel_filter=None):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # the filter of the ``pixel_size`` view: None or 'box' = the area pool of §20, today's kernels; 'bilinear', 'bicubic'
+        # or 'lanczos3': the antialiased resize the usual resizers apply (two kernels, one launch more per step).  It needs ``pixel_size``
+        # (or ``invert(pixel_target=)``) and takes neither a loss weight nor the hipGraph option
+        self.pixel_filter = check_pixel_filter(pixel_filter)
         # the size the pixel term is taken at: None = the image's own, today's kernels and launch list; an int: the term is the
         # mean of rho over the area-pooled residual (one fused kernel; with ``lpips_size`` of the same value both terms see one view).  A
         # low-resolution photograph enters nearest-upsampled: its area pool is the photograph.  Checked against the image size in ``invert``
@@ -1429,7 +1474,7 @@ class WPlusInverter:
         return self._pins[i]
 
     def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None, noise_ids=None,
-               latent_anchor=None, pn_stats=None):
+               latent_anchor=None, pn_stats=None, pixel_target=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
         then share the GPU with the matrix kernels of the other instead of running back to back.
@@ -1438,13 +1483,23 @@ class WPlusInverter:
         ``noise_ids``: int64 (B,), the id each image draws its latent noise under (default arange(B)); it travels with the image into the
         sub-batches, so an image sees the same noise on one stream or several and in any batch.  ``latent_anchor``: (L,512) or (B,L,512),
         what ``latent_reg`` pulls towards (required when latent_reg > 0).  ``pn_stats``: the ``oodgan.pn.PNStats`` of the mapping network on
-        the latents' device (required when pn_reg > 0; not looked at otherwise)."""
+        the latents' device (required when pn_reg > 0; not looked at otherwise).  ``pixel_target``: a float32 (B,C,n,n) image
+        on the device, the low-resolution target of the pixel term given at its own size; it fixes ``pixel_size`` = n (a differing
+        ``pixel_size`` is an error) and replaces the view of ``target`` made here — the pooled target with the box, the resized one with a
+        ``pixel_filter``.  ``target`` stays the full-size image LPIPS and SSIM, if on, compare with.  Not with a loss weight."""
         B = w0.shape[0]
         pn = pn_stats if check_pn(self.pn_reg, self.latent_space, pn_stats, int(w0.shape[-1]), w0.device, need_stats=True) != 0.0 else None
         size = check_lpips_size(self.lpips_size, int(target.shape[-1]))
         self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
-        psize = check_pixel_size(self.pixel_size, int(target.shape[-1]))
+        pixel_target, psize = check_pixel_target(pixel_target, target, self.pixel_size)
+        psize = check_pixel_size(psize, int(target.shape[-1]), 'pixel_size' if pixel_target is None else 'the size of pixel_target')
         self._pixel_f = 1 if psize is None else int(target.shape[-1]) // psize
+        if self.pixel_filter is not None and self._pixel_f == 1:
+            raise ValueError(f'pixel_filter {self.pixel_filter!r} needs pixel_size (or pixel_target) below the image size: at the image\'s own '
+                             f'size there is no view to filter')
+        if loss_weight is not None and (self.pixel_filter is not None or pixel_target is not None):
+            raise ValueError(f'a loss weight with {"pixel_filter" if self.pixel_filter is not None else "pixel_target"}: the masked objective '
+                             f'is taken on the area-pooled view of the full target only')
         if self._pixel_f > 1 and (target.shape[-2] % self._pixel_f or target.shape[-1] % self._pixel_f):
             raise ValueError(f'pixel_size {self.pixel_size}: the image {tuple(target.shape[-2:])} is not a multiple of the factor {self._pixel_f}')
         ids, anchor = self._sched_inputs(w0, noise_ids, latent_anchor)
@@ -1485,7 +1540,8 @@ class WPlusInverter:
             _lib.set_tunable('s1_big_min_items', MULTI_STREAM_S1_BIG_MIN_ITEMS)
         f0 = None if fshape is None else ops.zeros(B, *fshape, device=w0.device)
         try:
-            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0, pn)
+            return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0, pn,
+                                     pixel_target)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
@@ -1498,6 +1554,7 @@ class WPlusInverter:
                          (self.ssim_weight != 0.0, 'the SSIM term'),
                          (self.pixel_loss != 'mse', 'a robust pixel term'),
                          (self._pixel_f > 1, 'pixel_size'),
+                         (self.pixel_filter is not None, 'pixel_filter'),
                          (self.lr_rampup > 0.0 or self.lr_rampdown > 0.0 or self.latent_noise != 0.0 or self.latent_reg != 0.0,
                           'the projector schedule (lr ramps, latent noise, latent prior)'),
                          (self.latent_space != 'w+', f'latent_space {self.latent_space!r}'),
@@ -1526,8 +1583,8 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None):
-        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn)] per stream): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px)] per stream; ``px``, the pixel target, is sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
         ``pn``, the read-only statistics of the P_N+ prior, is shared by all of them.
         ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
         caller's own."""
@@ -1548,7 +1605,7 @@ class WPlusInverter:
                           [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous(),
                           None if ids is None else ids[sl].contiguous(),
                           anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor,
-                          None if f0 is None else f0[sl].contiguous(), pn))
+                          None if f0 is None else f0[sl].contiguous(), pn, None if px is None else px[sl].contiguous()))
         if on_side:
             for st in side:
                 st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
@@ -1573,11 +1630,12 @@ class WPlusInverter:
                     t.record_stream(cur)
         return out
 
-    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None, pn=None):
+    def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None, pn=None,
+                     px=None):
         self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
         replay = 'graph' if use_graph else 'plan' if self.use_plan else None
         # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
-        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn)
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px)
         runs = []
         try:
             for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):

@@ -1242,7 +1242,7 @@ ROBUST_KINDS = {'charbonnier': 1, 'huber': 2, 'geman_mcclure': 3}
 
 
 def pixel_loss_grad(img, target, kind='mse', scale=None, beta=None, grad_mul=1.0, wrt='gen', composite=False, loss_out=None, table=None,
-                    row_dev=None, grad=True, pool=1, target_pooled=None):
+                    row_dev=None, grad=True, pool=1, target_pooled=None, resample=None):
     """The pixel term of the W+ loss (csrc/loss_pixel.hip): per-image mean of rho(d), d = img - target or, with a loss weight
     ``beta`` (B,1,H,W), d = beta*(img - target) on the composite c = target + d (the masked objective).  ``kind``: 'mse' (rho = d^2; the gradient
     is grad_mul*2/CHW * d) or a robust term at ``scale`` s > 0, used as a float32 (the gradient is grad_mul/CHW * rho'(d)): 'charbonnier'
@@ -1257,10 +1257,24 @@ def pixel_loss_grad(img, target, kind='mse', scale=None, beta=None, grad_mul=1.0
     residual is r = area_pool(img) - ``target_pooled`` (``area_pool(target, f)``, made once by the caller; left out, it is pooled here, a
     convenience outside a step) or, with beta, r = area_pool(beta*(img - target)); the loss is the mean of rho(r) over the pooled pixels and
     every pixel of a window receives gscale * rho'(r) of its window, gscale as above (times beta(y,x) with ``wrt='gen'``); the gradient
-    and the composite stay (B,C,H,W).  ``pool=1`` (default) is the path above, untouched."""
+    and the composite stay (B,C,H,W).  ``pool=1`` (default) is the path above, untouched.
+    ``resample`` = (Ay, Ax) with ``pool`` = f: the term on the antialiased resampled view D(img) = Ay · img · Ax^T, the tables
+    those of ``resample_tables`` on the image's device (``resampled_pixel_loss_grad``: two kernels, the true gradient gscale' * Ay^T rho'(r) Ax
+    with gscale' = grad_mul / (C*Hs*Ws), twice that for 'mse').  ``target_pooled`` is the view of the target, D(target) or the caller's own
+    low-resolution image; left out, it is ``resample(target, Ay, Ax, f)``.  With ``beta`` it raises ValueError (the masked objective on a
+    resampled view is not built).  ``resample=None`` (default) is the code above, line for line."""
     a, t = _dev(img, 'img'), _dev(target, 'target')
     if kind != 'mse' and kind not in ROBUST_KINDS:
         raise ValueError(f"kind must be 'mse' or one of {sorted(ROBUST_KINDS)}, got {kind!r}")
+    if resample is not None:
+        if beta is not None or composite:
+            raise ValueError('resample: the masked objective (beta, composite) on a resampled view is not supported')
+        if _pool_factor(pool) == 1:
+            raise ValueError('resample needs pool = the factor of its tables, one of 2, 4, 8, 16')
+        Ay, Ax = resample
+        y = resample_view(t, Ay, Ax, pool) if target_pooled is None else target_pooled
+        loss, g, _ = resampled_pixel_loss_grad(a, y, Ay, Ax, pool, kind, scale, grad_mul, loss_out, table, row_dev, grad)
+        return loss, g, None
     if _pool_factor(pool) > 1:
         return _pooled_pixel_loss_grad(a, t, kind, scale, beta, grad_mul, wrt, composite, loss_out, table, row_dev, grad, pool, target_pooled)
     if target_pooled is not None:
@@ -1395,6 +1409,107 @@ def area_pool_bwd_add(gs, gimg, f):
                          f'{tuple(s.shape)} on {s.device}')
     check(_lib.lib().oodgan_area_pool_bwd_add(_p(s), _p(g), B * C, H, W, f, _stream()), 'area_pool_bwd_add')
     return gimg
+
+
+# support, in output pixels, of the named filters of ``resample_tables``
+RESAMPLE_FILTERS = {'bilinear': 2, 'bicubic': 4, 'lanczos3': 6}
+RESAMPLE_FACTORS = (2, 4, 8, 16)
+
+
+def _filter_taps(name, F):
+    """k[j] = phi((j + 1/2 - T/2) / F), j = 0 .. T-1, T = s*F, in float64."""
+    T = RESAMPLE_FILTERS[name] * F
+    t = ((torch.arange(T, dtype=torch.float64) + 0.5 - T / 2) / F).abs()
+    if name == 'bilinear':
+        return (1.0 - t).clamp_min(0.0)
+    if name == 'bicubic':                       # Keys, a = -0.5: the antialiased resizers' value
+        a = -0.5
+        near = ((a + 2.0) * t - (a + 3.0)) * t * t + 1.0
+        far = ((a * t - 5.0 * a) * t + 8.0 * a) * t - 4.0 * a
+        return torch.where(t <= 1.0, near, torch.where(t < 2.0, far, torch.zeros_like(t)))
+    return torch.where(t < 3.0, torch.sinc(t) * torch.sinc(t / 3.0), torch.zeros_like(t))
+
+
+def resample_tables(filter, H, F):
+    """The per-axis tap table of an antialiased resize of an axis of length H by the factor F in {2, 4, 8, 16}: a float32
+    (H/F, T) CPU tensor, T = s*F; output q reads inputs F*q - (T-F)/2 + j with weight A[q][j].  ``filter``: 'bilinear' (s = 2), 'bicubic'
+    (Keys, a = -0.5, s = 4), 'lanczos3' (s = 6) — what torch's ``F.interpolate(antialias=True)`` and PIL's ``resize`` compute — or a 1-D
+    sequence of s*F taps, s in {2, 4, 6}.  Taps outside [0, H) are dropped (weight 0) and the rest renormalised to sum 1; built in float64
+    and rounded to float32 once.  ValueError for anything else."""
+    if isinstance(F, bool) or not isinstance(F, int) or F not in RESAMPLE_FACTORS:
+        raise ValueError(f'the resample factor must be one of {list(RESAMPLE_FACTORS)}, got {F!r}')
+    if isinstance(H, bool) or not isinstance(H, int) or H < F or H % F != 0:
+        raise ValueError(f'the axis length must be a positive multiple of the factor {F}, got {H!r}')
+    if isinstance(filter, str):
+        if filter not in RESAMPLE_FILTERS:
+            raise ValueError(f'filter must be one of {sorted(RESAMPLE_FILTERS)} or a sequence of taps, got {filter!r}')
+        k = _filter_taps(filter, F)
+    else:
+        k = torch.as_tensor(filter, dtype=torch.float64).cpu()
+        if k.dim() != 1 or k.numel() not in [s * F for s in (2, 4, 6)] or not torch.isfinite(k).all():
+            raise ValueError(f'a tap sequence must be 1-D, finite and hold s*F = {[s * F for s in (2, 4, 6)]} taps for the factor {F}, '
+                             f'got shape {tuple(k.shape)}')
+    T = k.numel()
+    i = F * torch.arange(H // F)[:, None] - (T - F) // 2 + torch.arange(T)[None, :]
+    A = k[None, :] * ((i >= 0) & (i < H))
+    total = A.sum(dim=1, keepdim=True)
+    if not (total.abs() > 1e-12).all():
+        raise ValueError('a row of the table has no weight left after the taps outside the axis are dropped')
+    return (A / total).to(torch.float32)
+
+
+def _resample_tables_for(Ay, Ax, H, W, f, device):
+    """(Ay, Ax, s) as the kernels take them: contiguous float32 (H/f, s*f) and (W/f, s*f) tables on ``device``."""
+    f = _pool_factor(f)
+    out = []
+    for name, A, n in (('Ay', Ay, H // f), ('Ax', Ax, W // f)):
+        A = _dev(A, name)
+        if A.dim() != 2 or A.shape[0] != n or A.device != device or A.shape[1] != Ay.shape[1] or A.shape[1] not in (2 * f, 4 * f, 6 * f):
+            raise ValueError(f'{name} must be a ({n}, s*{f}) table on {device} with s in (2, 4, 6), both of one s, got {tuple(A.shape)} on '
+                             f'{A.device}')
+        out.append(A)
+    return out[0], out[1], out[0].shape[1] // f
+
+
+def resample_view(x, Ay, Ax, f):
+    """The antialiased resampled view of x (B,C,H,W): Ay · x · Ax^T per plane, (B,C,H/f,W/f) (oodgan_resample_fwd); Ay, Ax:
+    ``resample_tables`` of the two axes on x's device.  The same sums, bit for bit, as the view inside ``resampled_pixel_loss_grad``."""
+    a = _pool_image(x, 'x')
+    B, C, H, W = a.shape
+    Ay, Ax, s = _resample_tables_for(Ay, Ax, H, W, f, a.device)
+    y = torch.empty(B, C, H // f, W // f, device=a.device, dtype=torch.float32)
+    check(_lib.lib().oodgan_resample_fwd(_p(a), _p(Ay), _p(Ax), _p(y), B * C, H, W, f, s, _stream()), 'resample_fwd')
+    return y
+
+
+resample = resample_view
+
+
+def resampled_pixel_loss_grad(img, target_view, Ay, Ax, f, kind='mse', scale=None, grad_mul=1.0, loss_out=None, table=None, row_dev=None,
+                              grad=True):
+    """The pixel term on the resampled view (csrc/loss_resample.hip): r = Ay · img · Ax^T - ``target_view`` (B,C,H/f,W/f),
+    loss[b] = mean rho(r), gimg = grad_mul/(C*Hs*Ws) * Ay^T rho'(r) Ax (for 'mse' rho' = 2r).  Returns (loss[B] or None with ``table``,
+    gimg or None with ``grad=False`` — the same loss bit for bit —, psi(r) (B,C,H/f,W/f): r itself for 'mse').  The sinks as in
+    ``pixel_loss_grad``."""
+    a = _pool_image(_dev(img, 'img'), 'img')
+    if kind != 'mse' and kind not in ROBUST_KINDS:
+        raise ValueError(f"kind must be 'mse' or one of {sorted(ROBUST_KINDS)}, got {kind!r}")
+    B, C, H, W = a.shape
+    Ay, Ax, s = _resample_tables_for(Ay, Ax, H, W, f, a.device)
+    y = _dev(target_view, 'target_view')
+    if tuple(y.shape) != (B, C, H // f, W // f) or y.device != a.device:
+        raise ValueError(f'target_view must have shape {(B, C, H // f, W // f)} on {a.device}, got {tuple(y.shape)} on {y.device}')
+    L = _lib.lib()
+    part = torch.empty(B, max(1, L.oodgan_resampled_pixel_loss_nparts(C, H, W, f)), device=a.device, dtype=torch.float32)
+    psi = torch.empty_like(y)
+    g = torch.empty_like(a) if grad else None
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    sink = (_p(dst), _p(row), nrows) if by_row else (_p(dst),)
+    name = 'resampled_pixel_loss_fwd_bwd' + ('_row' if by_row else '')
+    check(getattr(L, 'oodgan_' + name)(_p(a), _p(y), _p(Ay), _p(Ax), _p(g), _p(psi), _p(part), *sink, B, C, H, W, f, s,
+                                       0 if kind == 'mse' else ROBUST_KINDS[kind], 0.0 if kind == 'mse' else float(scale), float(grad_mul),
+                                       _stream()), name)
+    return loss, g, psi
 
 
 def ssim_loss_grad(img, target, gimg=None, grad_mul=1.0, loss_out=None, table=None, row_dev=None):
