@@ -806,6 +806,35 @@ int oodgan_pn_prior_fwd_bwd(const float* w, const float* mu, const float* M, flo
 /* the same with the losses written to row min(row_dev[0], nrows-1) of loss_table (nrows, B), as oodgan_mse_fwd_bwd_row */
 int oodgan_pn_prior_fwd_bwd_row(const float* w, const float* mu, const float* M, float* g, float* loss_table, const int* row_dev, int nrows,
                                 int B, int L, int D, float weight, double* part, void* stream);
+/* Fitted out-of-domain mask of the W+ loop (csrc/loss_maskfit.hip; ABI 117).  The anchor is the reference's MaskLoss
+ * (src/losses/mask_loss.py with the settings of options/train/E4E_Face.yml:178-190), which shapes the mask its SAMM network predicts: an
+ * area hinge and a binarisation term.  Here the loop itself optimises, beside the latents, the logits l (B,1,m,m) of a low-resolution mask
+ * a = sigmoid(l); the loss weight of the composite objective is beta = U(a) (B,1,S,S), U exactly F.interpolate(a, size=(S,S),
+ * mode='bilinear', align_corners=False) — the call blending_mask makes (OOD_faceGAN_e4e_arch.py:330) —, and per image the mask carries
+ *   area_weight * max(0, mean(1 - a) - area) + binary_weight * mean(min(a, 1 - a)),
+ * MaskLoss with target 1 on alpha = 1 - a at the mask's own size (area_weight: its loss_weight; binary_weight: binary_weight * loss_weight).
+ * Shapes: S and m powers of two, 16 <= S <= 1024, 2 <= m <= 256, S / m >= 2; anything else is refused (-1).  Every entry launches kernels of
+ * this library only (a launch plan replays them), uses no float atomics and no memset / memcpy: two runs give identical bits.
+ * expand: a = sigmoid(l) and beta = U(a), once per step; beta 16-byte aligned. */
+int oodgan_maskfit_expand(const float* logit, float* a, float* beta, int B, int m, int S, void* stream);
+/* chain: one pass over gimg = dL/dc (B,C,S,S), the generator image, the target x and beta: e(p) = sum_c gimg_c(p) (G_c - x_c)(p) (channels
+ * in order, fused multiply-adds) to the plane e (B,1,S,S) = dL/dbeta, then gimg <- beta (.) gimg in place (what oodgan_scale_by_plane does
+ * for a frozen plane).  All pointers 16-byte aligned, 16 bytes per lane. */
+int oodgan_maskfit_chain(float* gimg, const float* gen, const float* x, const float* beta, float* e, int B, int C, int S, void* stream);
+/* step: the mask's side of a W+ step, launched BEFORE the latent-side call, which increments the counter: reads t_dev[0], does not
+ * increment it, uses t = t_dev[0] + 1 (as oodgan_feature_step).  e carries the loss scale grad_div.
+ *   mean(1 - a) and mean(min(a, 1 - a)) per image in double, two deterministic stages (a thread's cells in index order, then the block),
+ *   left in stat (2 B doubles); max(0, mean(1 - a) - area) and the binarisation mean, rounded once, go to row min(t - 1, nrows - 1) of
+ *   area_table / binary_table (nrows, B); a NULL table is not written;
+ *   U^T e per cell by gather: a cell reads its own separable tent support, at most 2F x 2F pixels, the clamped edge rows and columns landing
+ *   on the edge cells; sums in double, rounded once;
+ *   g = U^T e / grad_div - [mean(1 - a) > area] area_weight / m^2 + sign(1/2 - a) binary_weight / m^2 (torch's subgradients: 0 at either
+ *   tie), times da/dl = a (1 - a) taken from the logit; g is written: it holds what Adam consumed;
+ *   Adam on l as oodgan_feature_step, the same ramp factor r(t - 1) in double. */
+int oodgan_maskfit_step(float* logit, float* g, float* m, float* v, const float* a, const float* e, int B, int msize, int S, float lr,
+                        float beta1, float beta2, float eps, const int* t_dev, int total_steps, float rampup, float rampdown, float grad_div,
+                        float area, float area_weight, float binary_weight, float* area_table, float* binary_table, int nrows, double* stat,
+                        void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

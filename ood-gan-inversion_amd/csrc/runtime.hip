@@ -175,7 +175,7 @@ extern "C" int oodgan_plan_set_null_launch(int on) {
     return OODGAN_OK;
 }
 
-extern "C" int oodgan_version(void) { return 116; }      // 116: P_N+ prior of the W+ loop (oodgan_pn_prior_fwd_bwd[_row]); 115: feature offset of the W+ loop (oodgan_feature_add, oodgan_feature_step, oodgan_feature_step_nparts); 114: uint8 conversions and PSNR / SSIM of the command-line tool (oodgan_u8_to_input, oodgan_tensor2img_u8, oodgan_psnr_ssim_u8, oodgan_psnr_ssim_nparts); 113: area-pooled view for a loss term (oodgan_area_pool_fwd, oodgan_area_pool_bwd_add, dispatch counter "area_pool"); 112: robust pixel terms (oodgan_robust_loss_fwd_bwd[_row], dispatch counter "robust"); 111: SSIM loss term (oodgan_ssim_loss_fwd_bwd[_row], oodgan_ssim_nparts, dispatch counter "ssim"); 110: masked W+ loss (oodgan_composite_mse_fwd_bwd[_row], oodgan_scale_by_plane, oodgan_loss_weight_from_alpha, dispatch counter "composite_mse"); 109: oodgan_conv_args gained x_hi_only (precision f16s-g2), oodgan_plan_*, LPIPS ops; 108: oodgan_align_input / oodgan_align_input_stats gained `diff` (AlignNet diff_fAndg=False), dispatch sub-counters, tunable stripx_waves; 107: oodgan_conv_args gained dotx_sform / dotx_scale; 106: oodgan_conv_args gained ys_vmax (+ rgb_y partial sums / ys from the 8-wave stride-1 kernel), round-4 helpers; 105: oodgan_upconv_vblur_fform, oodgan_zero; 104: oodgan_dispatch_count / oodgan_dispatch_reset; 102: oodgan_conv_args gained x_fform, dotx_fform, workspace, workspace_bytes; 103: oodgan_blur_act_sform_sep
+extern "C" int oodgan_version(void) { return 117; }      // 117: fitted out-of-domain mask of the W+ loop (oodgan_maskfit_expand, oodgan_maskfit_chain, oodgan_maskfit_step); 116: P_N+ prior of the W+ loop (oodgan_pn_prior_fwd_bwd[_row]); 115: feature offset of the W+ loop (oodgan_feature_add, oodgan_feature_step, oodgan_feature_step_nparts); 114: uint8 conversions and PSNR / SSIM of the command-line tool (oodgan_u8_to_input, oodgan_tensor2img_u8, oodgan_psnr_ssim_u8, oodgan_psnr_ssim_nparts); 113: area-pooled view for a loss term (oodgan_area_pool_fwd, oodgan_area_pool_bwd_add, dispatch counter "area_pool"); 112: robust pixel terms (oodgan_robust_loss_fwd_bwd[_row], dispatch counter "robust"); 111: SSIM loss term (oodgan_ssim_loss_fwd_bwd[_row], oodgan_ssim_nparts, dispatch counter "ssim"); 110: masked W+ loss (oodgan_composite_mse_fwd_bwd[_row], oodgan_scale_by_plane, oodgan_loss_weight_from_alpha, dispatch counter "composite_mse"); 109: oodgan_conv_args gained x_hi_only (precision f16s-g2), oodgan_plan_*, LPIPS ops; 108: oodgan_align_input / oodgan_align_input_stats gained `diff` (AlignNet diff_fAndg=False), dispatch sub-counters, tunable stripx_waves; 107: oodgan_conv_args gained dotx_sform / dotx_scale; 106: oodgan_conv_args gained ys_vmax (+ rgb_y partial sums / ys from the 8-wave stride-1 kernel), round-4 helpers; 105: oodgan_upconv_vblur_fform, oodgan_zero; 104: oodgan_dispatch_count / oodgan_dispatch_reset; 102: oodgan_conv_args gained x_fform, dotx_fform, workspace, workspace_bytes; 103: oodgan_blur_act_sform_sep
 extern "C" const char* oodgan_last_error(void) { return oodgan::g_err; }
 extern "C" int oodgan_device_count(void) {
     int n = 0;

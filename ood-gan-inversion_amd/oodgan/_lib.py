@@ -17,7 +17,7 @@ ACT_NONE, ACT_LRELU, ACT_PRELU = 0, 1, 2
 P = c_void_p  # device pointers travel as integers
 
 
-ABI_VERSION = 116
+ABI_VERSION = 117
 
 
 class ConvArgs(Structure):
@@ -199,6 +199,10 @@ _SIGS = {
     'oodgan_feature_step_nparts': (c_int, [c_long]),
     'oodgan_feature_step': (c_int, [P, P, P, P, c_int, c_long, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, c_float, c_float, P,
                                     c_int, P, P]),
+    'oodgan_maskfit_expand': (c_int, [P, P, P, c_int, c_int, c_int, P]),
+    'oodgan_maskfit_chain': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P]),
+    'oodgan_maskfit_step': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, c_float,
+                                    c_float, c_float, c_float, P, P, c_int, P, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
     'oodgan_pn_prior_fwd_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P]),

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, mask_logits, refuse_mask_fit
 from .modules import Generator
 from .synth import generator_channels
 
@@ -269,7 +269,8 @@ class ood_faceGAN_e4e(nn.Module):
                ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, noise_ids=None, latent_reg=0.0,
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
                delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0,
-               pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, pixel_filter=None, pixel_target=None, **kwargs):
+               pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, pixel_filter=None, pixel_target=None, mask_size=64, mask_lr=0.1,
+               mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, mask_init=0.88, fit_blend=False, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -370,7 +371,38 @@ class ood_faceGAN_e4e(nn.Module):
         ``pixel_size`` = n.  ``x`` stays the full-size input of the encoder, the OOD forward and the blend, and LPIPS and SSIM, if on, keep
         comparing with ``x``.  A filter without a ``pixel_size`` below the image size, an unknown filter, a ``pixel_size`` that differs from
         the target's size, a size / n outside {2, 4, 8, 16}, or either option with ``loss_region`` other than 'full' raise ValueError;
-        ``use_graph`` with them NotImplementedError."""
+        ``use_graph`` with them NotImplementedError.
+        ``loss_region='fit'`` (the reference's MaskLoss, src/losses/mask_loss.py, is the anchor): the loop itself decides which
+        region it stops fitting.  Beside the latents it fits the logits of a mask a = sigmoid(l), (B,1,m,m) with m = ``mask_size`` in
+        {16, 32, 64, 128, 256} (S / m an integer >= 2); the loss is taken on the composite x + beta*(G(w) - x) with beta = the bilinear
+        enlargement of a (``F.interpolate(align_corners=False)``, what ``blending_mask`` applies), refreshed every step, plus per image
+        ``mask_area_weight`` * max(0, mean(1 - a) - ``mask_area``) + ``mask_binary_weight`` * mean(min(a, 1 - a)) — MaskLoss with target 1 on
+        alpha = 1 - a; the defaults 0.30 / 5.0 / 0.2 are the shipped YAML's area, loss_weight and binary_weight * loss_weight.  The logits
+        take Adam steps of their own at ``mask_lr`` (default 0.1) under the loop's betas, eps and ramps.  ``mask_init``: the start of a — a float
+        in (0, 1) (default 0.88), 'blend' (the beta of ``loss_region='blend'`` area-pooled to m x m; needs the modulation, as 'blend' does) or
+        a float32 (B,1,m,m) tensor in [0, 1] on the model's device; values are clipped to [1e-3, 1 - 1e-3] before the logit.  Afterwards
+        ``self.last_fitted_mask`` is a (B,1,m,m), ``self.last_loss_weight`` its enlargement beta (B,1,S,S), and
+        ``last_loss_terms['mask_area']`` / ``['mask_binary']`` the hinge and the binarisation mean per step and image (None when off).
+        ``fit_blend=True`` returns ``blend(x, G(w), alpha_scale=1 - beta)`` in place of the SAMM blend — the one OOD blend a model built with
+        ``enable_modulation=False`` has; False (default) leaves the returned image what it is without the option.  On a random-weight
+        generator the mask goes where an occluder is (tests/test_hip_mask_fit.py); quality on real faces is unpinned for lack of
+        checkpoints.  Goes with 'w+' / 'w', layer_lr, delta_reg, the schedule, pn_reg, edit, streams, the robust pixel terms, LPIPS and
+        SSIM.  ``use_graph``, pixel_size, pixel_filter / pixel_target, latent_space 's', feature_layer and a zero-padded (narrow) generator
+        raise NotImplementedError; a size outside the list or one that does not divide S, a negative or non-finite weight, a ``mask_lr``
+        that is not a finite number > 0, an area outside [0, 1], an init outside (0, 1) or of the wrong shape, dtype or device, and
+        ``fit_blend`` without 'fit' raise ValueError."""
+        fit = isinstance(loss_region, str) and loss_region == 'fit'
+        if fit:     # every check of the option before any device work; the refusals in one place (engine.refuse_mask_fit)
+            mask_size, mask_lr, mask_area, mask_area_weight, mask_binary_weight = check_mask_fit(
+                mask_size, mask_lr, mask_area, mask_area_weight, mask_binary_weight, int(x.shape[-1]))
+            mask_init = check_mask_init(mask_init, x.shape[0], mask_size, x.device)
+            if isinstance(mask_init, str) and (self.modulation is None or not self.blend_with_gen):
+                raise ValueError("mask_init='blend' needs enable_modulation=True and blend_with_gen=True: without them there is no blend")
+            refuse_mask_fit(use_graph, None if pixel_size == int(x.shape[-1]) else pixel_size, pixel_filter, pixel_target, latent_space,
+                            feature_layer)
+            refuse_mask_fit(padded=self.generator.engine().padded)
+        elif fit_blend:
+            raise ValueError("fit_blend needs loss_region='fit': there is no fitted mask to blend with")
         ssim_weight = check_nonneg(ssim_weight, 'ssim_weight')
         lr_rampup, lr_rampdown = check_nonneg(lr_rampup, 'lr_rampup'), check_nonneg(lr_rampdown, 'lr_rampdown')
         latent_noise, noise_ramp = check_nonneg(latent_noise, 'latent_noise'), check_nonneg(noise_ramp, 'noise_ramp')
@@ -398,7 +430,18 @@ class ood_faceGAN_e4e(nn.Module):
         edit = self._check_style_edit(edit, B, self.generator.engine().R, lats0.device) if sspace else self._check_edit(edit, lats0)
         if noise is None:
             noise = [n.expand(B, -1, -1, -1).contiguous() for n in self.generator.make_noise()]
-        beta = self._loss_weight(loss_region, x, lats0, enc_feats, noise)
+        ml0 = None
+        if fit:     # the start logits (set-up, not the step); the loop owns beta from here on
+            if isinstance(mask_init, torch.Tensor):
+                a0 = mask_init
+            elif isinstance(mask_init, str):
+                a0, f = self._loss_weight('blend', x, lats0, enc_feats, noise), int(x.shape[-1]) // mask_size
+                while f > 1:            # the area pool takes factors up to 16: a larger one in two passes, the same means
+                    a0, f = ops.area_pool(a0, min(f, 16)), f // min(f, 16)
+            else:
+                a0 = torch.full((B, 1, mask_size, mask_size), mask_init, device=x.device, dtype=torch.float32)
+            ml0 = mask_logits(a0)
+        beta = None if fit else self._loss_weight(loss_region, x, lats0, enc_feats, noise)
         self.last_loss_weight = beta
         lp = None
         if lpips_weight:
@@ -425,9 +468,13 @@ class ood_faceGAN_e4e(nn.Module):
                             lr_rampdown=lr_rampdown, latent_noise=sigma0, noise_ramp=noise_ramp, noise_seed=noise_seed, latent_reg=latent_reg,
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
                             delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size, feature_layer=feature_layer, feature_lr=feature_lr,
-                            feature_reg=feature_reg, pn_reg=pn_reg, pixel_filter=pixel_filter)
+                            feature_reg=feature_reg, pn_reg=pn_reg, pixel_filter=pixel_filter, mask_size=mask_size if fit else None,
+                            mask_lr=mask_lr, mask_area=mask_area, mask_area_weight=mask_area_weight, mask_binary_weight=mask_binary_weight)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
-                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target)
+                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target, mask_logits=ml0)
+        self.last_fitted_mask = inv.last_fitted_mask
+        if fit:
+            self.last_loss_weight = inv.last_loss_weight
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets',
                                                            'feature_offset')}
@@ -437,6 +484,12 @@ class ood_faceGAN_e4e(nn.Module):
         if sspace:          # w is the offset on the styles; the latents are the start's
             self.last_refined_lats, self.last_style_offsets = lats0, w
             out, lats = self._ood_forward(x, lats0, enc_feats, noise=noise, style_offsets=w if edit is None else (w + edit).contiguous(), **kw)
+        elif fit and fit_blend:     # the fitted mask's own blend in place of the SAMM blend: no hooks, so also without the modulation
+            self.last_refined_lats, self.last_style_offsets = w, None
+            lats = w if edit is None else (w + edit).contiguous()
+            self.ori_lats = lats
+            gen, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise)
+            out = self.blend(x, gen, alpha_scale=1.0 - self.last_loss_weight)
         else:
             self.last_refined_lats, self.last_style_offsets = w, None
             out, lats = self._ood_forward(x, w if edit is None else (w + edit).contiguous(), enc_feats, noise=noise, **kw)

@@ -14,8 +14,15 @@ in the same block advances the loop on S concurrent HIP streams, default 1; ``gr
 captured hipGraph).
 Where the W+ loss looks, in the same block:
 
-    loss_region: full | blend    full (default): every pixel.  blend: the blended output the model returns, x + beta*(G - x) with
-                                 beta = (1 - alpha)^blend_cnt from the mask of the OOD forward at the start latents.
+    loss_region: full | blend | fit    full (default): every pixel.  blend: the blended output the model returns, x + beta*(G - x) with
+                                 beta = (1 - alpha)^blend_cnt from the mask of the OOD forward at the start latents.  fit:
+                                 the loop fits a low-resolution mask beside the latents, under the reference's mask objective (an area
+                                 budget and a binarisation term), and weights the loss with it; its options, all optional:
+                                 mask_size (64; 16, 32, 64, 128 or 256, dividing the generator size by >= 2), mask_lr (0.1),
+                                 mask_area (0.30), mask_area_weight (5.0), mask_binary_weight (0.2), mask_init (0.88: a number in
+                                 (0, 1), or blend), fit_blend (false; true: the output is blended with the fitted mask instead of
+                                 the SAMM mask).  Not with mask_dir, pixel_size, pixel_filter / pixel_target, latent_space: s or
+                                 feature_layer.  A bad value is an error.
     mask_dir: <dir>              a caller mask per input file: <dir>/<base name>.png (grayscale; the first channel / 255 is beta,
                                  0 = ignore the pixel), resized nearest to the generator size.  A file without a mask is an error.
                                  Excludes ``loss_region: blend``.
@@ -104,7 +111,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, refuse_mask_fit
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -236,6 +243,34 @@ def feature_options(inv, n_latent=None):
                                             inv.get('latent_space', 'w+'), 'inversion.')
     check_feature_layer(layer, n_latent, 'inversion.feature_layer')
     return dict(feature_layer=layer, feature_lr=rate, feature_reg=reg)
+
+
+MASK_FIT_KEYS = ('mask_size', 'mask_lr', 'mask_area', 'mask_area_weight', 'mask_binary_weight', 'mask_init', 'fit_blend')
+
+
+def mask_fit_options(inv, image_size=None):
+    """``inversion.loss_region: fit`` and its keys (MASK_FIT_KEYS) for ``model.invert``, checked one by one (ValueError names the option;
+    NotImplementedError for what the fitted mask does not go with) — before the GPU is touched.  {} unless the region is 'fit'; any of the keys
+    without it is an error."""
+    if inv.get('loss_region', 'full') != 'fit':
+        stray = [k for k in MASK_FIT_KEYS if k in inv]
+        if stray:
+            raise ValueError(f'inversion.{stray[0]} needs inversion.loss_region: fit')
+        return {}
+    if inv.get('mask_dir'):
+        raise ValueError('inversion.mask_dir and inversion.loss_region: fit exclude each other')
+    m, rate, area, wa, wb = check_mask_fit(inv.get('mask_size', 64), inv.get('mask_lr', 0.1), inv.get('mask_area', 0.30),
+                                           inv.get('mask_area_weight', 5.0), inv.get('mask_binary_weight', 0.2), image_size, 'inversion.')
+    init = inv.get('mask_init', 0.88)
+    if isinstance(init, torch.Tensor):
+        raise ValueError("inversion.mask_init must be a number in (0, 1) or 'blend'")
+    init = check_mask_init(init, name='inversion.mask_init')
+    blend = inv.get('fit_blend', False)
+    if not isinstance(blend, bool):
+        raise ValueError(f'inversion.fit_blend must be true or false, got {blend!r}')
+    refuse_mask_fit(False, inv.get('pixel_size'), check_pixel_filter(inv.get('pixel_filter'), 'inversion.pixel_filter'),
+                    inv.get('pixel_target'), inv.get('latent_space', 'w+'), inv.get('feature_layer'))
+    return dict(mask_size=m, mask_lr=rate, mask_area=area, mask_area_weight=wa, mask_binary_weight=wb, mask_init=init, fit_blend=blend)
 
 
 def pn_options(inv):
@@ -380,10 +415,12 @@ def run(opts, wplus_steps=None, log=None):
     inv = opts.get('inversion') or {}
     io, io_workers = io_options(inv)
     loss_region, mask_dir = inv.get('loss_region', 'full'), inv.get('mask_dir')
-    if loss_region not in ('full', 'blend'):
-        raise ValueError(f"inversion.loss_region must be 'full' or 'blend', got {loss_region!r}")
-    if mask_dir and loss_region != 'full':
+    if loss_region not in ('full', 'blend', 'fit'):
+        raise ValueError(f"inversion.loss_region must be 'full', 'blend' or 'fit', got {loss_region!r}")
+    if mask_dir and loss_region == 'blend':
         raise ValueError('inversion.mask_dir and inversion.loss_region: blend exclude each other')
+    out_size0 = (opts.get('network_g') or {}).get('out_size')
+    fit_opts = mask_fit_options(inv, out_size0 if isinstance(out_size0, int) else None)
     ssim_weight = check_nonneg(inv.get('ssim_weight', 0.0), 'inversion.ssim_weight')
     pixel_loss, pixel_scale = check_pixel_loss(inv.get('pixel_loss', 'mse'), inv.get('pixel_scale', 0.1), 'inversion.pixel_loss',
                                                'inversion.pixel_scale')
@@ -401,6 +438,7 @@ def run(opts, wplus_steps=None, log=None):
     sched.update(style_options(inv))
     sched.update(feature_options(inv))
     sched.update(pn_options(inv))
+    sched.update(fit_opts)
     edit_at = edit_option(inv)
     steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     directions_dir = opts.get('directions_dir', './directions')
@@ -429,6 +467,7 @@ def run(opts, wplus_steps=None, log=None):
         raise ValueError(f'inversion.pixel_filter: {pixel_filter} needs inversion.pixel_size below the generator size {size}')
     latent_options(inv, model.generator.n_latent)
     feature_options(inv, model.generator.n_latent)
+    mask_fit_options(inv, size)
     summary = {}
     for name, dopt in opts['datasets'].items():
         files, direction = load_files_from_path(dopt, directions_dir)

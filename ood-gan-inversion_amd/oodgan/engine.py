@@ -853,7 +853,7 @@ class _WRun:
     repeated window draws the same noise and takes the same learning rates."""
 
     def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None, pn=None,
-                 px=None):
+                 px=None, ml0=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
@@ -923,10 +923,21 @@ class _WRun:
         self.pn = pn
         self.pn_table = torch.zeros(steps, self.w.shape[0], device=self.w.device, dtype=torch.float32) if inv.pn_reg != 0.0 else None
         self.pn_part = ops.pn_prior_parts(self.w.shape[0], self.w.shape[1], self.w.device) if self.pn_table is not None else None
+        # fitted mask: a third optimised state — the logits ``ml`` (B,1,m,m) from ``ml0``, their moments, the gradient Adam
+        # consumed, the mask a = sigmoid(ml), its enlargement ``beta`` (the loss weight of this run, rewritten by every step), the plane
+        # e = dL/dbeta, the per-image means and the two tables of the regulariser: all persistent and born here, never inside a recorded step
+        self.ml = self.mm = self.mv = self.mg = self.ma = self.me = self.mstat = self.ma_table = self.mb_table = None
+        if ml0 is not None:
+            Bm, S = self.w.shape[0], int(target.shape[-1])
+            self.ml = ml0.detach().clone().contiguous()
+            self.mm, self.mv, self.mg, self.ma = (torch.zeros_like(self.ml) for _ in range(4))
+            self.beta, self.me = (torch.empty(Bm, 1, S, S, device=self.w.device, dtype=torch.float32) for _ in range(2))
+            self.mstat = ops.maskfit_stat(Bm, self.w.device)
+            self.ma_table, self.mb_table = (torch.zeros(steps, Bm, device=self.w.device, dtype=torch.float32) for _ in range(2))
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
-        self.clean = (0, self.w.clone(), None, None, self._fsnap()) if self.guard else None     # m = v = 0 at t = 0
+        self.clean = (0, self.w.clone(), None, None, self._fsnap(), self._msnap()) if self.guard else None     # m = v = 0 at t = 0
         self.pending, self.exact_until = None, 0
         self.steps_run = 0                                       # forward/backward pairs enqueued, repeated windows included
         self.rollbacks = 0
@@ -963,7 +974,17 @@ class _WRun:
             # W: one vector of noise per image, repeated over the layers — the rows of w_in stay identical
             w_in = ops.latent_noise(self.w, self.dev_t, self.ids, self.steps, inv.latent_noise, inv.noise_ramp, inv.noise_seed, out=self.w_in,
                                     period=self.w.shape[-1] if self.tied else None)
-        if self.f is None:
+        if self.ml is not None:
+            # the fitted mask as a third leaf: a = sigmoid(ml) and beta = U(a) once per step, in front of the forward; ``_loss_grad`` leaves
+            # dL/dbeta in ``me``; the mask's side of the step stands BEFORE the latent-side call, which increments the counter both read
+            ops.maskfit_expand(self.ml, int(self.target.shape[-1]), a=self.ma, beta=self.beta)
+            img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
+            gimg = self._loss_grad(img)
+            g = eng.backward(gimg, self.gmul, carry_scale=True)
+            ops.maskfit_step(self.ml, self.mg, self.mm, self.mv, self.ma, self.me, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown,
+                             inv.mask_lr, inv.betas, inv.eps, grad_div=self.gmul, area=inv.mask_area, area_weight=inv.mask_area_weight,
+                             binary_weight=inv.mask_binary_weight, area_table=self.ma_table, binary_table=self.mb_table, stat=self.mstat)
+        elif self.f is None:
             img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
             gimg = self._loss_grad(img)
             g = eng.backward(gimg, self.gmul, carry_scale=True)
@@ -994,10 +1015,13 @@ class _WRun:
         the terms are taken on the composite c: alone, the composite MSE writes beta*dL/dc in one kernel; with LPIPS or
         SSIM it writes dL/dc and c, they add to it, and beta is applied once afterwards.  With ``pixel_size`` the pixel term is the fused
         kernel of the pooled view: the same call, the same number of launches, a full-resolution gradient and composite; with
-        ``pixel_filter`` the kernel pair of the antialiased view: the same call again, one launch more."""
+        ``pixel_filter`` the kernel pair of the antialiased view: the same call again, one launch more.  With a fitted mask
+         the pixel term always writes dL/dc (and c only if LPIPS or SSIM reads it), and ``maskfit_chain`` takes the place of
+        ``scale_by_plane``: the same pass also leaves dL/dbeta = sum_c dL/dc_c (G_c - x_c) in ``me``, whatever terms added to dL/dc."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
+        fit = self.ml is not None
         on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
-        _, gimg, c = ops.pixel_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if on_c else 'gen',
+        _, gimg, c = ops.pixel_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if (on_c or fit) else 'gen',
                                          composite=on_c, table=self.lbuf, row_dev=row, pool=self.px_f, target_pooled=self.px_target,
                                          resample=self.px_tables)
         x = c if on_c else img
@@ -1009,7 +1033,9 @@ class _WRun:
             ops.area_pool_bwd_add(gs, gimg, self.lp_f)
         if self.ss_table is not None:
             ops.ssim_loss_grad(x, self.target, gimg, inv.ssim_weight * gmul, table=self.ss_table, row_dev=row)
-        if on_c:
+        if fit:
+            ops.maskfit_chain(gimg, img, self.target, self.beta, e=self.me)
+        elif on_c:
             ops.scale_by_plane(gimg, self.beta)
         return gimg
 
@@ -1051,9 +1077,13 @@ class _WRun:
         """(f, fm, fv) as they stand, for a snapshot; None without a feature offset."""
         return None if self.f is None else (self.f.clone(), self.fm.clone(), self.fv.clone())
 
+    def _msnap(self):
+        """(ml, mm, mv) as they stand, for a snapshot; None without a fitted mask."""
+        return None if self.ml is None else (self.ml.clone(), self.mm.clone(), self.mv.clone())
+
     def _post_check(self):
         eng = self.eng
-        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap())
+        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap())
         ev = torch.cuda.Event()
         ev.record()
         side, done = _flag_stream(self.w.device), torch.cuda.Event()
@@ -1076,7 +1106,7 @@ class _WRun:
             self.clean = snap
             return False
         eng = self.eng
-        t0, w, m, v, fs = self.clean
+        t0, w, m, v, fs, ms = self.clean
         self.w.copy_(w)
         if m is None:
             self.m.zero_()
@@ -1086,6 +1116,9 @@ class _WRun:
             self.v.copy_(v)
         if fs is not None:                                       # the offset and its moments go back with the latents'
             for dst, src in zip((self.f, self.fm, self.fv), fs):
+                dst.copy_(src)
+        if ms is not None:                                       # ... and the mask's logits and theirs
+            for dst, src in zip((self.ml, self.mm, self.mv), ms):
                 dst.copy_(src)
         self.t = t0
         self.dev_t.fill_(t0)
@@ -1104,7 +1137,7 @@ class _WRun:
         eng.reset_fwd_state()
         self.exact_until = 0
         self.eager_left = self.warmup
-        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap())
+        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap())
 
     def _advance(self):
         if self.t < self.steps:
@@ -1362,6 +1395,78 @@ def check_pn_options(pn_reg, pn_samples=100000, pn_seed=0, pn_floor=0.0, latent_
     return reg, pn_samples, check_noise_seed(pn_seed, prefix + 'pn_seed'), check_nonneg(pn_floor, prefix + 'pn_floor')
 
 
+MASK_SIZES = (16, 32, 64, 128, 256)          # the sizes m of the fitted mask
+
+
+def _finite_real(value, name, what):
+    if isinstance(value, bool) or not isinstance(value, numbers.Real) or not math.isfinite(value):
+        raise ValueError(f'{name} must be {what}, got {value!r}')
+    return float(value)
+
+
+def check_mask_fit(mask_size=64, mask_lr=0.1, mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, image_size=None, prefix=''):
+    """The options of the fitted mask (loss_region='fit') as (m, lr, A, lambda_a, lambda_b): ValueError, naming the option,
+    unless ``mask_size`` is an int (not a bool) in MASK_SIZES and, once the image size S is known, S / m is an integer >= 2; ``mask_lr`` a
+    finite number > 0; ``mask_area`` a finite number in [0, 1]; the two weights finite numbers >= 0."""
+    if isinstance(mask_size, bool) or not isinstance(mask_size, int) or mask_size not in MASK_SIZES:
+        raise ValueError(f'{prefix}mask_size must be one of {list(MASK_SIZES)}, got {mask_size!r}')
+    if image_size is not None and (image_size % mask_size != 0 or image_size // mask_size < 2):
+        raise ValueError(f'{prefix}mask_size {mask_size} must divide the image size {image_size} by an integer >= 2')
+    rate = _finite_real(mask_lr, prefix + 'mask_lr', 'a finite number > 0')
+    if not rate > 0.0:
+        raise ValueError(f'{prefix}mask_lr must be a finite number > 0, got {mask_lr!r}')
+    area = _finite_real(mask_area, prefix + 'mask_area', 'a finite number in [0, 1]')
+    if not 0.0 <= area <= 1.0:
+        raise ValueError(f'{prefix}mask_area must be a finite number in [0, 1], got {mask_area!r}')
+    wa = _finite_real(mask_area_weight, prefix + 'mask_area_weight', 'a finite number >= 0')
+    wb = _finite_real(mask_binary_weight, prefix + 'mask_binary_weight', 'a finite number >= 0')
+    if wa < 0.0 or wb < 0.0:
+        raise ValueError(f'{prefix}mask_area_weight / {prefix}mask_binary_weight must be finite numbers >= 0, got {mask_area_weight!r}, {mask_binary_weight!r}')
+    return mask_size, rate, area, wa, wb
+
+
+def check_mask_init(value, B=None, m=None, device=None, name='mask_init'):
+    """``mask_init``, the start of beta: a float in (0, 1) (not a bool), the string 'blend', or a float32 (B,1,m,m) tensor on ``device``
+    (shape and device are checked once they are known; its values, which must lie in [0, 1], by ``mask_logits``).  ValueError otherwise."""
+    if isinstance(value, torch.Tensor):
+        if value.dtype != torch.float32 or value.dim() != 4:
+            raise ValueError(f'{name} tensor must be a float32 (B,1,m,m) tensor, got {value.dtype} {tuple(value.shape)}')
+        if B is not None and (tuple(value.shape) != (B, 1, m, m) or value.device != torch.device(device)):
+            raise ValueError(f'{name} tensor must be float32 of shape {(B, 1, m, m)} on {device}, got {tuple(value.shape)} on {value.device}')
+        return value
+    if isinstance(value, str):
+        if value != 'blend':
+            raise ValueError(f"{name} must be a float in (0, 1), 'blend' or a (B,1,m,m) tensor, got {value!r}")
+        return value
+    v = _finite_real(value, name, "a float in (0, 1), 'blend' or a (B,1,m,m) tensor")
+    if not 0.0 < v < 1.0:
+        raise ValueError(f'{name} must lie in (0, 1), got {value!r}')
+    return v
+
+
+MASK_INIT_CLIP = 1e-3
+
+
+def mask_logits(a0, name='mask_init'):
+    """The start logits of the fitted mask from a start mask a0 (B,1,m,m) with values in [0, 1] (ValueError otherwise; NaN fails): clipped
+    to [MASK_INIT_CLIP, 1 - MASK_INIT_CLIP], then log(a / (1 - a)).  Set-up, not the step."""
+    lo, hi = torch.aminmax(a0)
+    if not (lo.item() >= 0.0 and hi.item() <= 1.0):
+        raise ValueError(f'{name} values must lie in [0, 1], got [{lo.item()}, {hi.item()}]')
+    a = a0.detach().clamp(MASK_INIT_CLIP, 1.0 - MASK_INIT_CLIP)
+    return torch.log(a / (1.0 - a)).contiguous()
+
+
+def refuse_mask_fit(use_graph=False, pixel_size=None, pixel_filter=None, pixel_target=None, latent_space='w+', feature_layer=None, padded=False):
+    """What the fitted mask (loss_region='fit') does not go with, refused in this one place before anything is launched."""
+    for on, what in ((use_graph, 'use_graph'), (pixel_size is not None, 'pixel_size'), (pixel_filter is not None, 'pixel_filter'),
+                     (pixel_target is not None, 'pixel_target'), (latent_space == 's', "latent_space 's'"),
+                     (feature_layer is not None, 'feature_layer'),
+                     (padded, 'a generator whose channel counts are zero-padded to multiples of 16')):
+        if on:
+            raise NotImplementedError(f"loss_region='fit' with {what}: the fitted mask is built for the full-resolution pixel term of the 'w+' / 'w' loop under launch plans")
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1411,6 +1516,17 @@ class WPlusInverter:
     direction of W the same.  Evaluated at the unperturbed w, added to the gradient ``backward`` returned (``last_terms['pn']``); goes with
     'w+' and 'w', every other option and streams; refused with ``use_graph`` (NotImplementedError) and latent_space 's' (ValueError).
 
+    Fitted mask (the reference's MaskLoss, src/losses/mask_loss.py, is the anchor).  ``mask_size`` = m in MASK_SIZES: beside
+    the latents the loop fits the logits l (B,1,m,m) of a mask a = sigmoid(l), from ``invert(mask_logits=)``; the loss weight of the
+    composite objective is beta = U(a), U the bilinear enlargement of ``F.interpolate(align_corners=False)``, rewritten every step, and per
+    image the loss gains ``mask_area_weight`` * max(0, mean(1 - a) - ``mask_area``) + ``mask_binary_weight`` * mean(min(a, 1 - a)): the loop
+    decides which region, up to an area budget, it stops fitting.  Adam with ``mask_lr`` and the loop's betas, eps and ramps.  Results:
+    ``last_fitted_mask`` (a_T), ``last_mask_logits``, ``last_loss_weight`` (beta_T = U(a_T)), ``last_terms['mask_area']`` /
+    ``['mask_binary']`` (the hinge and the binarisation mean per step and image).  Goes with 'w+' and 'w', layer_lr, delta_reg, the schedule,
+    pn_reg, streams, the robust pixel terms, LPIPS (+ lpips_size) and SSIM; refused (``refuse_mask_fit``, NotImplementedError) with
+    ``use_graph``, pixel_size, pixel_filter / pixel_target, latent_space 's', feature_layer and a zero-padded generator; a caller's
+    ``loss_weight`` beside it raises ValueError.
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
@@ -1418,8 +1534,17 @@ class WPlusInverter:
     def __init__(self, engine, lr=0.01, betas=(0.9, 0.999), eps=1e-8, check_every=10, check_lag=2, use_plan=None, lpips=None, lpips_weight=0.0,
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
                  pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
-                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0, pixel_filter=None):
+                 pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0, pixel_filter=None, mask_size=None,
+                 mask_lr=0.1, mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # fitted mask, off by default (``mask_size`` None): the step is then the launch list above.  With a size m the loop
+        # fits the logits of an m x m mask beside the latents, under the reference's mask objective; the image size is known in ``invert``
+        self.mask_size = None
+        self.mask_lr, self.mask_area, self.mask_area_weight, self.mask_binary_weight = 0.1, 0.30, 5.0, 0.2
+        if mask_size is not None:
+            (self.mask_size, self.mask_lr, self.mask_area, self.mask_area_weight,
+             self.mask_binary_weight) = check_mask_fit(mask_size, mask_lr, mask_area, mask_area_weight, mask_binary_weight)
+        self.last_fitted_mask = self.last_mask_logits = self.last_loss_weight = None
         # the filter of the ``pixel_size`` view: None or 'box' = the area pool of §20, today's kernels; 'bilinear', 'bicubic'
         # or 'lanczos3': the antialiased resize the usual resizers apply (two kernels, one launch more per step).  It needs ``pixel_size``
         # (or ``invert(pixel_target=)``) and takes neither a loss weight nor the hipGraph option
@@ -1474,7 +1599,7 @@ class WPlusInverter:
         return self._pins[i]
 
     def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None, noise_ids=None,
-               latent_anchor=None, pn_stats=None, pixel_target=None):
+               latent_anchor=None, pn_stats=None, pixel_target=None, mask_logits=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
         then share the GPU with the matrix kernels of the other instead of running back to back.
@@ -1486,8 +1611,25 @@ class WPlusInverter:
         the latents' device (required when pn_reg > 0; not looked at otherwise).  ``pixel_target``: a float32 (B,C,n,n) image
         on the device, the low-resolution target of the pixel term given at its own size; it fixes ``pixel_size`` = n (a differing
         ``pixel_size`` is an error) and replaces the view of ``target`` made here — the pooled target with the box, the resized one with a
-        ``pixel_filter``.  ``target`` stays the full-size image LPIPS and SSIM, if on, compare with.  Not with a loss weight."""
+        ``pixel_filter``.  ``target`` stays the full-size image LPIPS and SSIM, if on, compare with.  Not with a loss weight.
+        ``mask_logits``: with ``mask_size`` = m, the float32 (B,1,m,m) start logits of the fitted mask on the device
+        (``mask_logits(a0)`` makes them from a start mask); required then, refused without it, and not beside a ``loss_weight``."""
         B = w0.shape[0]
+        self.last_fitted_mask = self.last_mask_logits = self.last_loss_weight = None
+        if self.mask_size is not None:
+            refuse_mask_fit(use_graph, None if self.pixel_size == int(target.shape[-1]) else self.pixel_size, self.pixel_filter, pixel_target, self.latent_space, self.feature_layer, self.engine.padded)
+            check_mask_fit(self.mask_size, self.mask_lr, self.mask_area, self.mask_area_weight, self.mask_binary_weight, int(target.shape[-1]))
+            if loss_weight is not None:
+                raise ValueError('a loss weight beside mask_size: the fitted mask IS the loss weight of the run')
+            m = self.mask_size
+            if (not isinstance(mask_logits, torch.Tensor) or tuple(mask_logits.shape) != (B, 1, m, m) or mask_logits.dtype != torch.float32
+                    or mask_logits.device != target.device):
+                raise ValueError(f'mask_logits must be a float32 {(B, 1, m, m)} tensor on {target.device} (mask_size {m})')
+            if target.shape[-1] != target.shape[-2]:
+                raise ValueError(f'mask_size: the image must be square, got {tuple(target.shape[-2:])}')
+            mask_logits = mask_logits.detach().contiguous()
+        elif mask_logits is not None:
+            raise ValueError('mask_logits without mask_size: there is no fitted mask they could start')
         pn = pn_stats if check_pn(self.pn_reg, self.latent_space, pn_stats, int(w0.shape[-1]), w0.device, need_stats=True) != 0.0 else None
         size = check_lpips_size(self.lpips_size, int(target.shape[-1]))
         self._lpips_f = 1 if size is None else int(target.shape[-1]) // size
@@ -1527,6 +1669,9 @@ class WPlusInverter:
             empty = torch.empty(0, B, device=w0.device, dtype=torch.float32)
             if fshape is not None:
                 self.last_feature_offset = torch.zeros((B,) + fshape, device=w0.device, dtype=torch.float32)
+            if self.mask_size is not None and B > 0:
+                self.last_mask_logits = mask_logits.clone()
+                self.last_fitted_mask, self.last_loss_weight = ops.maskfit_expand(self.last_mask_logits, int(target.shape[-1]))
             return (w, empty, []) if return_trajectory else (w, empty)
         if return_trajectory:
             streams, use_graph = 1, False
@@ -1541,7 +1686,7 @@ class WPlusInverter:
         f0 = None if fshape is None else ops.zeros(B, *fshape, device=w0.device)
         try:
             return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0, pn,
-                                     pixel_target)
+                                     pixel_target, mask_logits)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
@@ -1583,8 +1728,8 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None):
-        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px)] per stream; ``px``, the pixel target, is sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None, ml0=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px, ml0)] per stream; ``px``, the pixel target, and ``ml0``, the mask's start logits, are sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
         ``pn``, the read-only statistics of the P_N+ prior, is shared by all of them.
         ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
         caller's own."""
@@ -1605,17 +1750,18 @@ class WPlusInverter:
                           [n[sl].contiguous() if n.shape[0] == B else n for n in noises], None if beta is None else beta[sl].contiguous(),
                           None if ids is None else ids[sl].contiguous(),
                           anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor,
-                          None if f0 is None else f0[sl].contiguous(), pn, None if px is None else px[sl].contiguous()))
+                          None if f0 is None else f0[sl].contiguous(), pn, None if px is None else px[sl].contiguous(),
+                          None if ml0 is None else ml0[sl].contiguous()))
         if on_side:
             for st in side:
                 st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
         return side, engines, parts
 
     @staticmethod
-    def _gather(side, w, tables, f=None):
+    def _gather(side, w, tables, f=None, ml=None):
         """The per-stream latents (joined along the batch) and loss tables (``tables``: one list per term, None = term off; joined along the
         images) on the caller's stream; of a single run, its own tensors.  ``f``: the per-stream feature offsets, joined along the batch
-        like the latents and returned last."""
+        like the latents and returned after the tables; ``ml``: the per-stream mask logits, the same way, returned last."""
         cur = torch.cuda.current_stream()
         join = lambda ts, dim: ts[0] if len(ts) == 1 else torch.cat(ts, dim)
         for st in side:
@@ -1624,18 +1770,20 @@ class WPlusInverter:
         out = [join(w, 0)] + [None if ts[0] is None else join(ts, 1) for ts in tables]
         if f is not None:
             out.append(join(f, 0))
-        for ts in [w] + tables + ([] if f is None else [f]):     # tensors produced on side streams are consumed on the caller's stream
+        if ml is not None:
+            out.append(join(ml, 0))
+        for ts in [w] + tables + ([] if f is None else [f]) + ([] if ml is None else [ml]):     # tensors produced on side streams are consumed on the caller's stream
             for t in ts:
                 if t is not None:
                     t.record_stream(cur)
         return out
 
     def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None, pn=None,
-                     px=None):
+                     px=None, ml0=None):
         self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
         replay = 'graph' if use_graph else 'plan' if self.use_plan else None
         # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
-        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px)
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px, ml0)
         runs = []
         try:
             for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):
@@ -1656,7 +1804,12 @@ class WPlusInverter:
         self.last_plan = {'steps': [r.plan_steps for r in runs], 'launches': [r.plan_size for r in runs]}
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
                                                              [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs],
-                                                             [r.ft_table for r in runs], [r.pn_table for r in runs]], None if f0 is None else [r.f for r in runs])
+                                                             [r.ft_table for r in runs], [r.pn_table for r in runs], [r.ma_table for r in runs],
+                                                             [r.mb_table for r in runs]], None if f0 is None else [r.f for r in runs],
+                                 None if ml0 is None else [r.ml for r in runs])
+        if ml0 is not None:         # a_T and beta_T of the fitted logits: one more expand, outside the step
+            self.last_mask_logits = tables.pop()
+            self.last_fitted_mask, self.last_loss_weight = ops.maskfit_expand(self.last_mask_logits, int(target.shape[-1]))
         if f0 is not None:
             self.last_feature_offset = tables.pop()
         # a graph run has no per-window guard: its flags are read once, here, and a flagged inversion is repeated through the guarded loop
@@ -1665,13 +1818,15 @@ class WPlusInverter:
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None):
+    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None, ma=None, mb=None):
         self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl,
-                           'style': st, 'feature': ft, 'pn': pn}
+                           'style': st, 'feature': ft, 'pn': pn, 'mask_area': ma, 'mask_binary': mb}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         total = total if lat is None else total + self.latent_reg * lat
         total = total if dl is None else total + self.delta_reg * dl
         total = total if st is None else total + self.style_reg * st
         total = total if ft is None else total + self.feature_reg * ft
-        return total if pn is None else total + self.pn_reg * pn
+        total = total if pn is None else total + self.pn_reg * pn
+        total = total if ma is None else total + self.mask_area_weight * ma
+        return total if mb is None else total + self.mask_binary_weight * mb

@@ -1848,3 +1848,79 @@ def feature_step(delta, g, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, l
                                          _p(t_dev), int(total_steps), float(rampup), float(rampdown), float(grad_div), float(feature_reg),
                                          _p(dst), nrows, _p(part if dst is not None else None), _stream()), 'feature_step')
     return delta
+
+
+# ---- fitted out-of-domain mask of the W+ loop (csrc/loss_maskfit.hip)
+def _mask_cells(t, name):
+    """t as the mask ops take it: a contiguous float32 (B,1,m,m) tensor on the device (no copy: the step updates in place)."""
+    a = _dev(t, name)
+    if a.dim() != 4 or a.shape[1] != 1 or a.shape[2] != a.shape[3] or not t.is_contiguous() or t.dtype != torch.float32:
+        raise ValueError(f'{name} must be a contiguous float32 (B,1,m,m) tensor, got {t.dtype} {tuple(t.shape)}')
+    return t
+
+
+def maskfit_expand(logit, size, a=None, beta=None):
+    """a = sigmoid(logit) (B,1,m,m) and beta = F.interpolate(a, size=(S,S), mode='bilinear', align_corners=False) (B,1,S,S)
+    (oodgan_maskfit_expand).  ``a`` / ``beta``: contiguous float32 buffers of those shapes to write into (the W+ loop's persistent ones);
+    None: new tensors.  S and m powers of two, 16 <= S <= 1024, 2 <= m <= 256, S / m >= 2: the library refuses anything else.  Returns (a, beta)."""
+    l = _mask_cells(logit, 'logit')
+    B, m, S = l.shape[0], l.shape[2], int(size)
+    a = torch.empty_like(l) if a is None else a
+    beta = torch.empty(B, 1, S, S, device=l.device, dtype=torch.float32) if beta is None else beta
+    assert a.shape == l.shape and a.dtype == torch.float32 and a.is_contiguous() and a.device == l.device, 'maskfit_expand: a'
+    assert tuple(beta.shape) == (B, 1, S, S) and beta.dtype == torch.float32 and beta.is_contiguous() and beta.device == l.device, 'maskfit_expand: beta'
+    check(_lib.lib().oodgan_maskfit_expand(_p(l), _p(a), _p(beta), B, m, S, _stream()), 'maskfit_expand')
+    return a, beta
+
+
+def maskfit_chain(gimg, gen, target, beta, e=None):
+    """One pass over gimg = dL/dc, the generator image, the target and beta (oodgan_maskfit_chain): e = sum_c gimg_c * (gen_c - target_c),
+    (B,1,S,S), the gradient w.r.t. beta; then gimg <- beta * gimg in place, the gradient w.r.t. the generator image.  Returns (gimg, e)."""
+    assert gimg.is_contiguous(), 'maskfit_chain: gimg must be contiguous (it is updated in place)'
+    g, a, t = _dev(gimg, 'gimg'), _dev(gen, 'gen'), _dev(target, 'target')
+    if g.dim() != 4 or g.shape != a.shape or g.shape != t.shape or g.shape[2] != g.shape[3]:
+        raise ValueError(f'maskfit_chain: gimg, gen and target must be (B,C,S,S) of one shape, got {tuple(g.shape)}, {tuple(a.shape)}, {tuple(t.shape)}')
+    w = _plane(beta, g)
+    B, C, S, _ = g.shape
+    e = torch.empty(B, 1, S, S, device=g.device, dtype=torch.float32) if e is None else e
+    assert tuple(e.shape) == (B, 1, S, S) and e.dtype == torch.float32 and e.is_contiguous() and e.device == g.device, 'maskfit_chain: e'
+    check(_lib.lib().oodgan_maskfit_chain(_p(gimg), _p(a), _p(t), _p(w), _p(e), B, C, S, _stream()), 'maskfit_chain')
+    return gimg, e
+
+
+def maskfit_stat(B, device):
+    """The (B, 2) float64 buffer ``maskfit_step`` leaves mean(1 - a) and mean(min(a, 1 - a)) in."""
+    return torch.empty(B, 2, device=device, dtype=torch.float64)
+
+
+def maskfit_step(logit, g, m, v, a, e, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.1, betas=(0.9, 0.999), eps=1e-8, grad_div=1.0,
+                 area=0.30, area_weight=5.0, binary_weight=0.2, area_table=None, binary_table=None, stat=None):
+    """The mask's side of a W+ step (oodgan_maskfit_step): logit, g, m, v (B,1,m,m) contiguous float32, updated in place; ``a`` the mask of
+    ``maskfit_expand``, ``e`` (B,1,S,S) the plane of ``maskfit_chain``, which carries ``grad_div``.  g receives
+    (U^T e / grad_div + the gradients of area_weight * max(0, mean(1 - a) - area) + binary_weight * mean(min(a, 1 - a))) * a(1 - a), what
+    Adam consumes.  Like ``feature_step`` it reads ``t_dev``, uses t = t_dev[0] + 1 and leaves the counter alone: it runs BEFORE the
+    latent-side call.  The hinge and the binarisation mean go to row t_dev[0] (clamped) of ``area_table`` / ``binary_table`` (nrows, B).
+    ``stat``: the buffer of ``maskfit_stat`` (made here when None).  Returns logit."""
+    l = _mask_cells(logit, 'logit')
+    B, ms = l.shape[0], l.shape[2]
+    for t, name in ((g, 'g'), (m, 'm'), (v, 'v'), (a, 'a')):
+        assert isinstance(t, torch.Tensor) and t.shape == l.shape and t.dtype == torch.float32 and t.is_contiguous() and t.device == l.device, \
+            f'maskfit_step: {name} must be a contiguous float32 tensor of the logits\' shape on their device'
+    ee = _dev(e, 'e')
+    if ee.dim() != 4 or tuple(ee.shape[:2]) != (B, 1) or ee.shape[2] != ee.shape[3] or not e.is_contiguous():
+        raise ValueError(f'maskfit_step: e must be a contiguous (B,1,S,S) tensor, got {tuple(ee.shape)}')
+    assert t_dev.dtype == torch.int32 and t_dev.device == l.device
+    nrows = 0
+    for tb in (area_table, binary_table):
+        if tb is not None:
+            assert tb.dim() == 2 and tb.shape[1] == B and tb.dtype == torch.float32 and tb.is_contiguous() and tb.device == l.device
+            assert nrows in (0, tb.shape[0]), 'maskfit_step: the two tables must have one number of rows'
+            nrows = tb.shape[0]
+    if stat is None:
+        stat = maskfit_stat(B, l.device)
+    assert stat.dtype == torch.float64 and stat.is_contiguous() and stat.device == l.device and stat.numel() >= 2 * B, 'maskfit_step: stat'
+    check(_lib.lib().oodgan_maskfit_step(_p(logit), _p(g), _p(m), _p(v), _p(a), _p(e), B, ms, int(ee.shape[2]), float(lr), float(betas[0]),
+                                         float(betas[1]), float(eps), _p(t_dev), int(total_steps), float(rampup), float(rampdown),
+                                         float(grad_div), float(area), float(area_weight), float(binary_weight), _p(area_table),
+                                         _p(binary_table), nrows, _p(stat), _stream()), 'maskfit_step')
+    return logit
