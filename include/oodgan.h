@@ -52,6 +52,9 @@ int oodgan_device_count(void);
  *                                                    (csrc/conv_f16s_stripx.hip, round 3); 8 = two waves per SIMD, the K loop split over a wave pair with
  *                                                    de-phased producer / finisher roles (csrc/experimental/conv_f16s_stripx8.hip, round 5: measured equal — retired from the default
  *                                                    build in round 6: only in a library built with `make STRIPX8=1`, OODGAN_E_ARG otherwise)
+ *   "blurt_seg_rows"   OODGAN_BLURT_SEG_ROWS   0     v > 0: the strip walk of oodgan_act_bwd_blurT_sform_phases cuts the height into segments of max(v, 16) position
+ *                                                    rows (nseg = ceil((H+1) / rows), still <= the slot table's rows) instead of the occupancy rule — the unit tests walk
+ *                                                    the segment heights of the large layers (18, 19, 35, 74: odd ones take the single-step tail in every segment) on small tensors
  * oodgan_set_tunable returns OODGAN_E_ARG for an unknown name; oodgan_get_tunable returns -1 for one. */
 int oodgan_set_tunable(const char* name, long value);
 long oodgan_get_tunable(const char* name);
@@ -60,7 +63,8 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) and "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]).  Host-side, one relaxed atomic increment per call; the reference has no
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) and "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]); the backward producers: "blurt_strip" / "blurt_tile" (launches of the
+ * strip walk / the tile kernel of oodgan_act_bwd_blurT_sform_phases[_hi]), "actbwd_sform" (oodgan_act_bwd_sform) and "actbwd_sform_f" (oodgan_act_bwd_sform_f).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
 long oodgan_dispatch_count(const char* name);

@@ -959,6 +959,7 @@ extern "C" int oodgan_act_bwd_sform(const float* g_feat, const float* out, const
     OODGAN_REQUIRE((long)B * yd.KC <= 65535, "act_bwd_sform: B*C too large");
     hipLaunchKernelGGL(act_bwd_sform_kernel, dim3(a.nparts, B * yd.KC), dim3(256), 0, as_stream(stream), a,
                        reinterpret_cast<uint4*>(ys), yd);
+    count_dispatch(OODGAN_DC_ACTBWD_SFORM);
     return check_launch("act_bwd_sform");
 }
 
@@ -977,6 +978,7 @@ extern "C" int oodgan_act_bwd_sform_f(const float* out_f, const float* noise, in
     OODGAN_REQUIRE((long)B * yd.KC <= 65535, "act_bwd_sform_f: B*C too large");
     hipLaunchKernelGGL(act_bwd_sform_f_kernel, dim3(a.nparts, B * yd.KC), dim3(256), 0, as_stream(stream), a,
                        reinterpret_cast<uint4*>(ys), yd);
+    count_dispatch(OODGAN_DC_ACTBWD_SFORM_F);
     return check_launch("act_bwd_sform_f");
 }
 
@@ -1059,6 +1061,9 @@ static int act_bwd_blurT_impl(const float* g_feat, const float* out, const float
         if (nseg < 1) nseg = 1;
         int seg_rows = (int)((H + 1 + nseg - 1) / nseg);
         if (seg_rows < 16) seg_rows = 16;
+        // tunable blurt_seg_rows > 0 (tests): the segment height itself, so that small tensors walk the odd segment heights of the 1024² layer
+        const long forced = oodgan::tunable(oodgan::OODGAN_TUN_BLURT_SEG_ROWS);
+        if (forced > 0) seg_rows = (int)(forced < 16 ? 16 : (forced > H + 1 ? H + 1 : forced));
         geo.seg_rows = seg_rows;
         geo.nseg = (H + 1 + seg_rows - 1) / seg_rows;
         OODGAN_REQUIRE(geo.nseg <= tiles_y && geo.nstrips <= tiles_x, "act_bwd_blurT strip: slot table too small");
@@ -1072,6 +1077,7 @@ static int act_bwd_blurT_impl(const float* g_feat, const float* out, const float
             if (out) OODGAN_STRIP_LAUNCH(false, false); else OODGAN_STRIP_LAUNCH(false, true);
         }
 #undef OODGAN_STRIP_LAUNCH
+        count_dispatch(OODGAN_DC_BLURT_STRIP);
         return check_launch("act_bwd_blurT_sform_phases/strip");
     }
     OODGAN_REQUIRE(!hi_only, "act_bwd_blurT hi-only records: not reachable (strip walk refused this call)");
@@ -1081,6 +1087,7 @@ static int act_bwd_blurT_impl(const float* g_feat, const float* out, const float
     else
         hipLaunchKernelGGL(act_bwd_blurT_sp_kernel<false>, dim3((unsigned)nb), dim3(256), 0, as_stream(stream), a, kernel,
                            reinterpret_cast<uint4*>(out_phases), H, W, d, tiles_x, tiles_y);
+    count_dispatch(OODGAN_DC_BLURT_TILE);
     return check_launch("act_bwd_blurT_sform_phases");
 }
 

@@ -33,7 +33,7 @@ namespace oodgan {
 void set_error(const char* fmt, ...);
 
 // dispatch tunables (runtime.hip): environment default read once, then oodgan_set_tunable
-enum { OODGAN_TUN_S1_BIG_MIN_ITEMS = 0, OODGAN_TUN_S2_BIG_MIN_ITEMS, OODGAN_TUN_T2_BIG_MIN_ITEMS, OODGAN_TUN_BLURT_STRIP, OODGAN_TUN_BLUR_STRIP, OODGAN_TUN_UPVB_WAVES, OODGAN_TUN_FEWOUT_QUAD, OODGAN_TUN_TINY_MID_MAX, OODGAN_TUN_STRIPX_WAVES, OODGAN_TUN_COUNT };
+enum { OODGAN_TUN_S1_BIG_MIN_ITEMS = 0, OODGAN_TUN_S2_BIG_MIN_ITEMS, OODGAN_TUN_T2_BIG_MIN_ITEMS, OODGAN_TUN_BLURT_STRIP, OODGAN_TUN_BLUR_STRIP, OODGAN_TUN_UPVB_WAVES, OODGAN_TUN_FEWOUT_QUAD, OODGAN_TUN_TINY_MID_MAX, OODGAN_TUN_STRIPX_WAVES, OODGAN_TUN_BLURT_SEG_ROWS, OODGAN_TUN_COUNT };
 long tunable(int id);
 
 // dispatch counters (runtime.hip, oodgan_dispatch_count): which kernel family a conv call was routed to — tests assert that the
@@ -58,7 +58,9 @@ enum { OODGAN_DC_STRIPX = 0, OODGAN_DC_STRIP, OODGAN_DC_S1BIG, OODGAN_DC_S1V2, O
        // calls of the P_N+ prior (latent_pn.hip, oodgan_pn_prior_fwd_bwd[_row])
        OODGAN_DC_PN,
        // calls of the resampled pixel term (loss_resample.hip, oodgan_resampled_pixel_loss_fwd_bwd[_row])
-       OODGAN_DC_RESAMPLED_PIXEL, OODGAN_DC_COUNT };
+       OODGAN_DC_RESAMPLED_PIXEL,
+       // launches of the backward producers (bwd_producers.hip): blur^T strip walk / blur^T tile kernel / oodgan_act_bwd_sform / oodgan_act_bwd_sform_f
+       OODGAN_DC_BLURT_STRIP, OODGAN_DC_BLURT_TILE, OODGAN_DC_ACTBWD_SFORM, OODGAN_DC_ACTBWD_SFORM_F, OODGAN_DC_COUNT };
 void count_dispatch(int id);
 
 // One process per GPU: per-kernel setup (dynamic-LDS attributes, the zero page and CU count of the F-form strip

@@ -261,7 +261,7 @@ def set_tunable(name, value):
 
 
 def dispatch_count(name):
-    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", the area-pool kernels, "area_pool", the pooled pixel-term kernel, "pooled_pixel", or the resampled pixel term, "resampled_pixel") since load /
+    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", the area-pool kernels, "area_pool", the pooled pixel-term kernel, "pooled_pixel", or the resampled pixel term, "resampled_pixel", or launches of the backward producers, "blurt_strip" / "blurt_tile" / "actbwd_sform" / "actbwd_sform_f") since load /
     dispatch_reset() (include/oodgan.h)."""
     n = lib().oodgan_dispatch_count(name.encode())
     if n < 0:

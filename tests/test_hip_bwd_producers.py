@@ -61,14 +61,26 @@ def test_act_bwd_sform_matches_two_pass(B, C, H, W, rgb):
     assert flag.item() == 1 and torch.equal(bad, mul2)
 
 
-@pytest.mark.parametrize('B,C,H,W,rgb', [(2, 32, 8, 8, False), (1, 16, 4, 4, False), (1, 40, 18, 32, True)])
-def test_act_bwd_blurT_phases_matches_two_pass(B, C, H, W, rgb):
+def _blur_kernel(kern, dev):
+    """'sym': the generator's [1,3,3,1] x [1,3,3,1]; 'r1': outer([1,2,4,1], [1,3,3,2]) * 4/72 (tests/bwd_producer_ref.py) — rank one too, but neither
+    palindromic nor symmetric: a path that flips or swaps its vertical and horizontal taps no longer agrees with the other."""
+    from oracle import ref_cpu as R
+    from bwd_producer_ref import blur_kernel
+    if kern == 'r1':
+        return blur_kernel('r1').to(dev)
+    return torch.flip(R.make_kernel([1, 3, 3, 1]) * 4.0, [0, 1]).contiguous().to(dev)
+
+
+@pytest.mark.parametrize('B,C,H,W,rgb,kern', [pytest.param(2, 32, 8, 8, False, 'sym', id='2-32-8-8-False'), pytest.param(1, 16, 4, 4, False, 'sym', id='1-16-4-4-False'),
+                                              pytest.param(1, 40, 18, 32, True, 'sym', id='1-40-18-32-True'), pytest.param(2, 32, 8, 8, False, 'r1', id='2-32-8-8-False-r1'),
+                                              pytest.param(1, 16, 4, 4, False, 'r1', id='1-16-4-4-False-r1'), pytest.param(1, 40, 18, 32, True, 'r1', id='1-40-18-32-True-r1')])
+def test_act_bwd_blurT_phases_matches_two_pass(B, C, H, W, rgb, kern):
     """H,W = input size of the up-conv; the activations are (2H,2W)."""
     from oodgan import ops
     from oracle import ref_cpu as R
     dev = torch.device('cuda:0')
     out, g_feat, noise, nw, bias, d, kw = _inputs(B, C, 2 * H, 2 * W, 5 + C, rgb, dev)
-    k = torch.flip(R.make_kernel([1, 3, 3, 1]) * 4.0, [0, 1]).contiguous().to(dev)
+    k = _blur_kernel(kern, dev)
     if rgb:
         g_pre, r0, t0, mul2 = ops.act_bwd_fused(out, g_feat, noise, nw, bias, kw['g_rgb'], kw['w_rgb'], kw['s_rgb'], want_scale=True, dscale=d)
     else:
@@ -202,16 +214,17 @@ def test_s2_conv_with_fused_activation_backward(B, Co, Ci, H, W, rgb, tunable):
         assert (g_feat2 - g_feat).abs().max().item() <= 1e-6 * g_feat.abs().max().item() and (dot3 - dot0).abs().max().item() <= 1e-5 * dot0.abs().max().item()
 
 
-@pytest.mark.parametrize('B,C,H,W,sep', [(1, 32, 32, 32, True), (2, 16, 40, 64, True), (1, 48, 37, 66, True), (1, 24, 64, 34, False), (1, 16, 33, 128, True)])
+@pytest.mark.parametrize('B,C,H,W,sep', [(1, 32, 32, 32, True), (2, 16, 40, 64, True), (1, 48, 37, 66, True), (1, 24, 64, 34, False), (1, 16, 33, 128, True),
+                                         (1, 32, 32, 32, 'r1'), (2, 16, 40, 64, 'r1'), (1, 48, 37, 66, 'r1'), (1, 16, 33, 128, 'r1')])
 def test_act_bwd_blurT_strip_walk_matches_two_pass_and_tile_kernel(B, C, H, W, sep, tunable):
     """The strip-walking form of the blur^T producer (up-sampling layers with H, W >= 32 and no ToRGB branch) against the
     two-pass path (act_bwd_fused -> blurT_to_sform_phases) and against the tile kernel; ragged strips / segments, partial
-    channel blocks, and a kernel that is not rank-1."""
+    channel blocks, a kernel that is not rank-1 (sep False), and a rank-1 kernel that is neither palindromic nor symmetric (sep 'r1')."""
     from oodgan import ops
     from oracle import ref_cpu as R
     dev = torch.device('cuda:0')
     out, g_feat, noise, nw, bias, d, kw = _inputs(B, C, 2 * H, 2 * W, 9 + C, False, dev)
-    k = torch.flip(R.make_kernel([1, 3, 3, 1]) * 4.0, [0, 1]).contiguous()
+    k = _blur_kernel('r1' if sep == 'r1' else 'sym', dev).cpu()
     if not sep:
         k[1, 2] += 0.37
         k[3, 0] -= 0.11
