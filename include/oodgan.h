@@ -63,7 +63,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) and "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]); the backward producers: "blurt_strip" / "blurt_tile" (launches of the
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]) and "align" (accepted calls of oodgan_similarity_warp / oodgan_align_grad_step); the backward producers: "blurt_strip" / "blurt_tile" (launches of the
  * strip walk / the tile kernel of oodgan_act_bwd_blurT_sform_phases[_hi]), "actbwd_sform" (oodgan_act_bwd_sform) and "actbwd_sform_f" (oodgan_act_bwd_sform_f).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
@@ -839,6 +839,37 @@ int oodgan_maskfit_step(float* logit, float* g, float* m, float* v, const float*
                         float beta1, float beta2, float eps, const int* t_dev, int total_steps, float rampup, float rampdown, float grad_div,
                         float area, float area_weight, float binary_weight, float* area_table, float* binary_table, int nrows, double* stat,
                         void* stream);
+/* Similarity alignment of the target beside the latents of the W+ loop (csrc/loss_align.hip; entries added, ABI 117
+ * unchanged).  The reference compares G(w) with the photograph in the generator's canonical frame and has no counterpart; the resampler is
+ * F.grid_sample(src, F.affine_grid([[a, -s, tx], [s, a, ty]], align_corners=False), mode='bicubic', padding_mode='border',
+ * align_corners=False) with a = e^lambda cos(phi), s = e^lambda sin(phi).  theta (B, 4) float32 = (lambda, phi, tx, ty) per image: log-scale,
+ * rotation in radians, translation in affine_grid's normalised units (1 = half the image side).  With cx = (W-1)/2, cy = (H-1)/2, output
+ * pixel (X, Y) of a plane (H, W) samples src at (X + du, Y + dv),
+ *   du = (a-1)(X-cx) - s (W/H)(Y-cy) + tx W/2,   dv = s (H/W)(X-cx) + (a-1)(Y-cy) + ty H/2,
+ * a-1, s and the offsets formed in double from the float32 theta; du clamped to [-2-X, W+1-X], dv likewise (no value changes under border
+ * padding, every index stays finite for any theta, NaN and inf included: a NaN offset goes to the lower end); i0 = X + floor(du),
+ * tau = du - floor(du) rounded to float32 once; taps i0-1 .. i0+2 clamped to [0, W-1]; Keys' cubic weights (A = -0.75) at distances
+ * 1+tau, tau, 1-tau, 2-tau; the same in y; the value is the separable 16-tap sum (rows first, left to right, then top to bottom, fp32, no
+ * contraction).  theta = 0: the weights are (0, 1, 0, 0) and out == src bit for bit.
+ * warp: out (B, C, H, W) = the warp of src by theta; out must not be src.  Coalesced stores, the gather reads src. */
+int oodgan_similarity_warp(const float* src, const float* theta, float* out, int B, int C, int H, int W, void* stream);
+/* Partial sums per image of oodgan_align_grad_step (one per block of 1024 pixels, six doubles each); 0: H or W outside [4, 32768]. */
+int oodgan_align_grad_nparts(int H, int W);
+/* The alignment's side of a W+ step.  gimg (B, C, H, W) is the image gradient of the step, dL/dG times the loss scale grad_div; the target
+ * enters every pixel term as G - x_theta (or P(G) - P(x_theta) on a pooled view), so dL/dx_theta = -gimg and
+ *   dL/dtheta_k = -sum_{c,p} gimg_c(p) (dx_theta/du du/dtheta_k + dx_theta/dv dv/dtheta_k) / grad_div,
+ * autograd's gradient of the definition above (the cubic is C1).  The taps are gathered again from src (no derivative planes in HBM).  Two
+ * deterministic stages, no float atomics: six double sums per block of 1024 pixels (a thread's pixels in index order, the wave's xor tree,
+ * the four waves in order) to `part` (B, oodgan_align_grad_nparts, 6) doubles, the caller's; then one wave per image adds them in double,
+ * forms the four derivatives and rounds once.  align_reg = mu >= 0: g_k += 2 mu theta_k, the gradient of mu sum_k theta_k^2; that sum
+ * (before the update) goes to row min(t - 1, nrows - 1) of reg_table (nrows, B), NULL: not written.  g (B, 4) is written: it holds what Adam
+ * consumed.  Adam on theta with m, v (B, 4) as oodgan_feature_step: the same betas, eps and ramp factor r(t - 1) in double; launched BEFORE
+ * the latent-side call of the step, it reads t_dev[0], uses t = t_dev[0] + 1 and does NOT increment.  lr 0 leaves theta as it is.
+ * Both entries: a null pointer, B C <= 0, H or W < 4, lr < 0 (or NaN), align_reg < 0, grad_div <= 0: -1 and nothing is launched.  Counted
+ * by the dispatch counter "align" (every accepted call of either entry). */
+int oodgan_align_grad_step(const float* gimg, const float* src, float* theta, float* g, float* m, float* v, int B, int C, int H, int W,
+                           float lr, float beta1, float beta2, float eps, const int* t_dev, int total_steps, float rampup, float rampdown,
+                           float grad_div, float align_reg, float* reg_table, int nrows, double* part, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

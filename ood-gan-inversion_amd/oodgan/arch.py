@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, mask_logits, refuse_mask_fit
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, mask_logits, refuse_mask_fit, check_align, check_align_init, refuse_align
 from .modules import Generator
 from .synth import generator_channels
 
@@ -270,7 +270,8 @@ class ood_faceGAN_e4e(nn.Module):
                latent_anchor='start', pixel_loss='mse', pixel_scale=0.1, lpips_size=None, edit=None, latent_space='w+', layer_lr=None,
                delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0,
                pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, pixel_filter=None, pixel_target=None, mask_size=64, mask_lr=0.1,
-               mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, mask_init=0.88, fit_blend=False, **kwargs):
+               mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, mask_init=0.88, fit_blend=False, align=None, align_lr=0.001,
+               align_reg=0.0, align_init=None, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -390,7 +391,42 @@ class ood_faceGAN_e4e(nn.Module):
         SSIM.  ``use_graph``, pixel_size, pixel_filter / pixel_target, latent_space 's', feature_layer and a zero-padded (narrow) generator
         raise NotImplementedError; a size outside the list or one that does not divide S, a negative or non-finite weight, a ``mask_lr``
         that is not a finite number > 0, an area outside [0, 1], an init outside (0, 1) or of the wrong shape, dtype or device, and
-        ``fit_blend`` without 'fit' raise ValueError."""
+        ``fit_blend`` without 'fit' raise ValueError.
+        ``align='similarity'``: the loop fits, beside the latents, a similarity theta = (log-scale, rotation in radians, tx, ty
+        in units of half the image side) per image and compares G(w) with x warped by it — a photograph a few pixels or a degree off the
+        generator's canonical frame is registered instead of costing the latents.  Adam with ``align_lr`` (0.001: about half a pixel per
+        step at 1024²; nobody has measured it as an optimum) under the loop's betas, eps and ramps; ``align_reg`` = mu >= 0 adds
+        mu * sum_k theta_k^2 per image (``last_loss_terms['align']``); ``align_init``: a float32 (B,4) start on the device, None = the
+        identity.  After the loop x_a = ``ops.similarity_warp(x, theta)``: the encoder features of the final OOD forward are taken from x_a
+        (on a model with modulation blocks: by the attached encoder, or by ``enc_feats`` given as a callable x_a -> features; ``enc_feats``
+        given as tensors, the features of x, or neither, raises ValueError before the loop starts)
+        and the forward and the blend run on x_a, so THE OUTPUT IS IN THE ALIGNED FRAME (``ops.similarity_warp(out,
+        ops.similarity_inverse(theta))`` maps it back); ``self.last_alignment`` is theta (B,4), ``self.last_aligned_input`` x_a (both None
+        without the option).  Goes with 'w+' / 'w', layer_lr, delta_reg, the schedule, pn_reg, edit, streams, the four pixel kinds and box
+        ``pixel_size``.  ``use_graph``, LPIPS, SSIM, a ``loss_region`` other than 'full', a non-box ``pixel_filter``, ``pixel_target``,
+        latent_space 's', feature_layer and a zero-padded (narrow) generator raise NotImplementedError (``engine.refuse_align``); a bad name,
+        rate, weight or start raises ValueError."""
+        align, align_lr, align_reg = check_align(align, align_lr, align_reg)
+        feats_of = None
+        if align is not None:       # every check of the option before any device work; the refusals in one place (engine.refuse_align)
+            region = loss_region if isinstance(loss_region, str) else 'a loss-weight tensor'
+            refuse_align(use_graph, bool(lpips_weight), ssim_weight != 0.0, region, pixel_filter, pixel_target, latent_space, feature_layer)
+            refuse_align(padded=self.generator.engine().padded)
+            check_align_init(align_init, x.shape[0], x.device)
+            # the final OOD forward needs the encoder features of x_a, which does not exist before the loop: an attached encoder delivers
+            # them, or the caller's ``enc_feats`` is a callable x_a -> features; features handed in as tensors are those of x
+            if self.modulation is not None:
+                ef = kwargs.get('enc_feats')
+                if callable(ef):
+                    feats_of = ef
+                elif ef is not None:
+                    raise ValueError('align with enc_feats given as tensors: they are the features of x, and the final OOD forward needs those of '
+                                     'the aligned input x_a; pass enc_feats=<callable x_a -> features> or attach an encoder')
+                elif isinstance(self.encoder, _MissingEncoder):
+                    raise ValueError('align on a model with modulation blocks needs the encoder features of the aligned input: attach an encoder '
+                                     'or pass enc_feats=<callable x_a -> features>')
+        elif align_init is not None:
+            raise ValueError('align_init without align: there is no alignment it could start')
         fit = isinstance(loss_region, str) and loss_region == 'fit'
         if fit:     # every check of the option before any device work; the refusals in one place (engine.refuse_mask_fit)
             mask_size, mask_lr, mask_area, mask_area_weight, mask_binary_weight = check_mask_fit(
@@ -469,10 +505,17 @@ class ood_faceGAN_e4e(nn.Module):
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
                             delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size, feature_layer=feature_layer, feature_lr=feature_lr,
                             feature_reg=feature_reg, pn_reg=pn_reg, pixel_filter=pixel_filter, mask_size=mask_size if fit else None,
-                            mask_lr=mask_lr, mask_area=mask_area, mask_area_weight=mask_area_weight, mask_binary_weight=mask_binary_weight)
+                            mask_lr=mask_lr, mask_area=mask_area, mask_area_weight=mask_area_weight, mask_binary_weight=mask_binary_weight, align=align, align_lr=align_lr, align_reg=align_reg)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
-                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target, mask_logits=ml0)
+                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target, mask_logits=ml0, align_init=align_init)
         self.last_fitted_mask = inv.last_fitted_mask
+        self.last_alignment, self.last_aligned_input = inv.last_alignment, inv.last_aligned_target
+        if align is not None:       # the output is made in the aligned frame: the encoder features, the forward and the blend see x_a
+            x = self.last_aligned_input
+            if feats_of is not None:
+                enc_feats = feats_of(x)
+            elif self.modulation is not None:
+                _, enc_feats = self.encode(x, **{k: v for k, v in kwargs.items() if k not in ('enc_lats', 'enc_feats')})
         if fit:
             self.last_loss_weight = inv.last_loss_weight
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan

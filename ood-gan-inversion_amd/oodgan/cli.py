@@ -23,6 +23,14 @@ Where the W+ loss looks, in the same block:
                                  (0, 1), or blend), fit_blend (false; true: the output is blended with the fitted mask instead of
                                  the SAMM mask).  Not with mask_dir, pixel_size, pixel_filter / pixel_target, latent_space: s or
                                  feature_layer.  A bad value is an error.
+    align: similarity            the loop fits, beside the latents, a similarity (log-scale, rotation, translation) per image and compares
+                                 G(w) with the input warped by it: a photograph a few pixels or a degree off the generator's
+                                 canonical frame is registered instead of costing the latents.  The saved inversion is in the ALIGNED frame,
+                                 while the metrics still compare it with the input file in ITS frame: with this option they are taken
+                                 across two frames and understate the fit (a warning says so once per run).
+                                 align_lr (0.001: about half a pixel per step at 1024²; not a measured optimum; >= 0), align_reg (0:
+                                 the weight of sum theta^2; >= 0).  Not with lpips_weight, ssim_weight, loss_region other than full,
+                                 mask_dir, a non-box pixel_filter, pixel_target, latent_space: s or feature_layer.  A bad value is an error.
     mask_dir: <dir>              a caller mask per input file: <dir>/<base name>.png (grayscale; the first channel / 255 is beta,
                                  0 = ignore the pixel), resized nearest to the generator size.  A file without a mask is an error.
                                  Excludes ``loss_region: blend``.
@@ -111,7 +119,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, refuse_mask_fit
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, refuse_mask_fit, check_align, refuse_align
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -271,6 +279,26 @@ def mask_fit_options(inv, image_size=None):
     refuse_mask_fit(False, inv.get('pixel_size'), check_pixel_filter(inv.get('pixel_filter'), 'inversion.pixel_filter'),
                     inv.get('pixel_target'), inv.get('latent_space', 'w+'), inv.get('feature_layer'))
     return dict(mask_size=m, mask_lr=rate, mask_area=area, mask_area_weight=wa, mask_binary_weight=wb, mask_init=init, fit_blend=blend)
+
+
+ALIGN_KEYS = ('align', 'align_lr', 'align_reg')
+
+
+def align_options(inv):
+    """``inversion.align`` / ``align_lr`` / ``align_reg`` for ``model.invert``, checked one by one (ValueError names the option;
+    NotImplementedError for what the alignment does not go with) — before the GPU is touched.  {} without ``align``; either of the other
+    two without it is an error."""
+    if inv.get('align') is None:
+        stray = [k for k in ALIGN_KEYS[1:] if k in inv]
+        if stray:
+            raise ValueError(f'inversion.{stray[0]} needs inversion.align')
+        return {}
+    kind, rate, reg = check_align(inv['align'], inv.get('align_lr', 0.001), inv.get('align_reg', 0.0), 'inversion.')
+    lpips_weight, ssim_weight = inv.get('lpips_weight', 0.0), inv.get('ssim_weight', 0.0)
+    refuse_align(False, bool(lpips_weight), bool(ssim_weight), 'mask_dir' if inv.get('mask_dir') else inv.get('loss_region', 'full'),
+                 check_pixel_filter(inv.get('pixel_filter'), 'inversion.pixel_filter'), inv.get('pixel_target'), inv.get('latent_space', 'w+'),
+                 inv.get('feature_layer'))
+    return dict(align=kind, align_lr=rate, align_reg=reg)
 
 
 def pn_options(inv):
@@ -439,6 +467,7 @@ def run(opts, wplus_steps=None, log=None):
     sched.update(feature_options(inv))
     sched.update(pn_options(inv))
     sched.update(fit_opts)
+    sched.update(align_options(inv))
     edit_at = edit_option(inv)
     steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     directions_dir = opts.get('directions_dir', './directions')
@@ -453,6 +482,9 @@ def run(opts, wplus_steps=None, log=None):
     streams = int(inv.get('streams', 1))
     lpips_weight = float(inv.get('lpips_weight', 0.0))       # opt-in perceptual term of the W+ loss (oodgan/lpips.py)
     lpips_state = torch.load(inv['lpips_path'], map_location='cpu') if inv.get('lpips_path') else None
+    if sched.get('align') is not None and opts.get('metrics'):
+        log.warning('inversion.align: the saved inversions are in the aligned frame, the metrics compare them with the input files in their own '
+                    'frame — they are taken across two frames')
     if lpips_weight and lpips_state is None:
         log.warning('inversion.lpips_weight without inversion.lpips_path: the LPIPS term runs on SEEDED AlexNet / lin weights (the lpips package\'s '
                     'pretrained weights are not part of this build)')

@@ -853,9 +853,23 @@ class _WRun:
     repeated window draws the same noise and takes the same learning rates."""
 
     def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None, pn=None,
-                 px=None, ml0=None):
+                 px=None, ml0=None, th0=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
+        # similarity alignment (DESIGN.md §25): a leaf beside the latents — theta (B,4) from ``th0``, its moments and the gradient Adam consumed.
+        # ``src`` keeps the photograph; ``target`` becomes the buffer x_theta the warp rewrites in front of every forward, so that
+        # ``_loss_grad`` reads it where it read the photograph (with ``pixel_size`` the pooled target below is re-made from it every step as
+        # well).  All persistent and born here, never inside a recorded step (see ``replay`` below); ``align_reg`` brings a loss table
+        self.src = self.th = self.thm = self.thv = self.thg = self.apart = self.al_table = None
+        if th0 is not None:
+            self.src = target.contiguous()
+            self.target = target = torch.empty_like(self.src)
+            self.th = th0.detach().clone().contiguous()
+            self.thm, self.thv, self.thg = (torch.zeros_like(self.th) for _ in range(3))
+            self.apart = ops.align_grad_parts(self.th.shape[0], self.src.shape[-2], self.src.shape[-1], self.src.device)
+            ops.similarity_warp(self.src, self.th, out=self.target)       # what the set-up below pools: every step warps again
+            if inv.align_reg != 0.0:
+                self.al_table = torch.zeros(steps, self.th.shape[0], device=self.th.device, dtype=torch.float32)
         # masked objective (DESIGN.md §5): the per-image loss weight plane (B,1,S,S), a persistent input like ``target`` (a recorded step
         # replays it unchanged; a rollback needs nothing new: it is constant for the run); None = the plain per-image MSE
         self.beta = beta
@@ -937,7 +951,7 @@ class _WRun:
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
-        self.clean = (0, self.w.clone(), None, None, self._fsnap(), self._msnap()) if self.guard else None     # m = v = 0 at t = 0
+        self.clean = (0, self.w.clone(), None, None, self._fsnap(), self._msnap(), self._asnap()) if self.guard else None     # m = v = 0 at t = 0
         self.pending, self.exact_until = None, 0
         self.steps_run = 0                                       # forward/backward pairs enqueued, repeated windows included
         self.rollbacks = 0
@@ -984,6 +998,19 @@ class _WRun:
             ops.maskfit_step(self.ml, self.mg, self.mm, self.mv, self.ma, self.me, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown,
                              inv.mask_lr, inv.betas, inv.eps, grad_div=self.gmul, area=inv.mask_area, area_weight=inv.mask_area_weight,
                              binary_weight=inv.mask_binary_weight, area_table=self.ma_table, binary_table=self.mb_table, stat=self.mstat)
+        elif self.th is not None:
+            # the alignment as a second leaf: the photograph is warped by theta into ``target`` (and pooled into ``px_target``) in front of the
+            # forward, the loss and the backward are the plain step's, and dL/dtheta is read off the image gradient the step computed
+            # anyway; its side of the step stands BEFORE the latent-side call, which increments the counter both read
+            ops.similarity_warp(self.src, self.th, out=self.target)
+            if self.px_f > 1:
+                ops.area_pool(self.target, self.px_f, out=self.px_target)
+            img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
+            gimg = self._loss_grad(img)
+            g = eng.backward(gimg, self.gmul, carry_scale=True)
+            ops.align_grad_step(gimg, self.src, self.th, self.thg, self.thm, self.thv, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown,
+                                inv.align_lr, inv.betas, inv.eps, grad_div=self.gmul, align_reg=inv.align_reg, table=self.al_table,
+                                part=self.apart)
         elif self.f is None:
             img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
             gimg = self._loss_grad(img)
@@ -1081,9 +1108,13 @@ class _WRun:
         """(ml, mm, mv) as they stand, for a snapshot; None without a fitted mask."""
         return None if self.ml is None else (self.ml.clone(), self.mm.clone(), self.mv.clone())
 
+    def _asnap(self):
+        """(th, thm, thv) as they stand, for a snapshot; None without an alignment."""
+        return None if self.th is None else (self.th.clone(), self.thm.clone(), self.thv.clone())
+
     def _post_check(self):
         eng = self.eng
-        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap())
+        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap(), self._asnap())
         ev = torch.cuda.Event()
         ev.record()
         side, done = _flag_stream(self.w.device), torch.cuda.Event()
@@ -1106,7 +1137,7 @@ class _WRun:
             self.clean = snap
             return False
         eng = self.eng
-        t0, w, m, v, fs, ms = self.clean
+        t0, w, m, v, fs, ms, als = self.clean
         self.w.copy_(w)
         if m is None:
             self.m.zero_()
@@ -1119,6 +1150,9 @@ class _WRun:
                 dst.copy_(src)
         if ms is not None:                                       # ... and the mask's logits and theirs
             for dst, src in zip((self.ml, self.mm, self.mv), ms):
+                dst.copy_(src)
+        if als is not None:                                      # ... and the alignment and its moments
+            for dst, src in zip((self.th, self.thm, self.thv), als):
                 dst.copy_(src)
         self.t = t0
         self.dev_t.fill_(t0)
@@ -1137,7 +1171,7 @@ class _WRun:
         eng.reset_fwd_state()
         self.exact_until = 0
         self.eager_left = self.warmup
-        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap())
+        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap(), self._asnap())
 
     def _advance(self):
         if self.t < self.steps:
@@ -1467,6 +1501,53 @@ def refuse_mask_fit(use_graph=False, pixel_size=None, pixel_filter=None, pixel_t
             raise NotImplementedError(f"loss_region='fit' with {what}: the fitted mask is built for the full-resolution pixel term of the 'w+' / 'w' loop under launch plans")
 
 
+ALIGN_KINDS = ('similarity',)        # the alignments the W+ loop fits beside the latents
+
+
+def check_align(align=None, align_lr=0.001, align_reg=0.0, prefix=''):
+    """The options of the fitted alignment as (align, align_lr, align_reg): ValueError, naming the option, unless ``align`` is
+    None or one of ALIGN_KINDS, ``align_lr`` a finite number >= 0 (0 keeps theta at its start: the run then is the plain run on the target
+    warped once) and ``align_reg`` a finite number >= 0.  Without ``align`` the other two are not looked at."""
+    if align is None:
+        return None, 0.001, 0.0
+    if not isinstance(align, str) or align not in ALIGN_KINDS:
+        raise ValueError(f'{prefix}align must be None or one of {list(ALIGN_KINDS)}, got {align!r}')
+    rate = _finite_real(align_lr, prefix + 'align_lr', 'a finite number >= 0')
+    reg = _finite_real(align_reg, prefix + 'align_reg', 'a finite number >= 0')
+    if rate < 0.0 or reg < 0.0:
+        raise ValueError(f'{prefix}align_lr / {prefix}align_reg must be finite numbers >= 0, got {align_lr!r}, {align_reg!r}')
+    return align, rate, reg
+
+
+def check_align_init(value, B=None, device=None, name='align_init'):
+    """``align_init``, the start of theta: None (the identity) or a float32 (B, 4) tensor of finite values — (log-scale, rotation in radians,
+    tx, ty) per image — on ``device`` (batch and device are checked once they are known).  ValueError otherwise."""
+    if value is None:
+        return None
+    if not isinstance(value, torch.Tensor) or value.dtype != torch.float32 or value.dim() != 2 or value.shape[1] != 4:
+        raise ValueError(f'{name} must be None or a float32 (B, 4) tensor (log-scale, rotation, tx, ty), got '
+                         f'{getattr(value, "dtype", type(value).__name__)} {tuple(getattr(value, "shape", ()))}')
+    if B is not None and (value.shape[0] != B or value.device != torch.device(device)):
+        raise ValueError(f'{name} must be a float32 {(B, 4)} tensor on {device}, got {tuple(value.shape)} on {value.device}')
+    if not bool(torch.isfinite(value).all()):
+        raise ValueError(f'{name} must hold finite values')
+    return value
+
+
+def refuse_align(use_graph=False, lpips=False, ssim=False, loss_region='full', pixel_filter=None, pixel_target=None, latent_space='w+',
+                 feature_layer=None, padded=False):
+    """What the fitted alignment does not go with, refused in this one place before anything is launched.  Two of the
+    reasons: LPIPS caches the target's taps, and a loss weight or a fitted mask lives in the photograph's frame, not in the warped one."""
+    for on, what in ((use_graph, 'use_graph'), (lpips, 'the LPIPS term'), (ssim, 'the SSIM term'),
+                     (loss_region != 'full', f'loss_region {loss_region!r} (a loss weight or a fitted mask)'),
+                     (pixel_filter not in (None, 'box'), f'pixel_filter {pixel_filter!r}'), (pixel_target is not None, 'pixel_target'),
+                     (latent_space == 's', "latent_space 's'"), (feature_layer is not None, 'feature_layer'),
+                     (padded, 'a generator whose channel counts are zero-padded to multiples of 16')):
+        if on:
+            raise NotImplementedError(f"align with {what}: the alignment is built for the pixel term (every kind, full resolution or box "
+                                      f"pixel_size) of the 'w+' / 'w' loop under launch plans")
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1527,6 +1608,17 @@ class WPlusInverter:
     ``use_graph``, pixel_size, pixel_filter / pixel_target, latent_space 's', feature_layer and a zero-padded generator; a caller's
     ``loss_weight`` beside it raises ValueError.
 
+    Fitted alignment.  ``align='similarity'``: beside the latents the loop fits theta = (log-scale, rotation in radians, tx, ty
+    in units of half the image side) per image, from ``invert(align_init=)`` (None: the identity), and every step compares G(w) with the
+    target warped by theta (bicubic, border padding; ``ops.similarity_warp``) — a photograph a few pixels or a degree off the generator's
+    canonical frame is registered instead of being explained by the latents.  The target is warped, not the generator image: forward,
+    backward and the pixel-term kernels are the plain step's, and dL/dtheta is read off the image gradient.  Adam with ``align_lr`` (0.001:
+    about half a pixel per step at 1024²; not a measured optimum) and the loop's betas, eps and ramps; ``align_reg`` = mu >= 0 adds
+    mu * sum_k theta_k^2 per image (``last_terms['align']``).  Results: ``last_alignment`` (B,4), ``last_aligned_target``.  Goes with 'w+' and
+    'w', layer_lr, delta_reg, the schedule, pn_reg, the four pixel kinds, box ``pixel_size`` and streams; refused (``refuse_align``,
+    NotImplementedError) with ``use_graph``, LPIPS, SSIM, a loss weight or a fitted mask, pixel_filter / pixel_target, latent_space 's',
+    feature_layer and a zero-padded generator.
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
@@ -1535,8 +1627,14 @@ class WPlusInverter:
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
                  pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
                  pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0, pixel_filter=None, mask_size=None,
-                 mask_lr=0.1, mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2):
+                 mask_lr=0.1, mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, align=None, align_lr=0.001, align_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # fitted alignment, off by default (``align`` None): the step is then the launch list above.  'similarity': beside the
+        # latents the loop fits theta = (log-scale, rotation, tx, ty) per image and compares G(w) with the target warped by it.  The default
+        # rate 0.001 moves a translation by about half a pixel per step at 1024² (tx is in units of half the image side); nobody has
+        # measured it as an optimum
+        self.align, self.align_lr, self.align_reg = check_align(align, align_lr, align_reg)
+        self.last_alignment = self.last_aligned_target = None
         # fitted mask, off by default (``mask_size`` None): the step is then the launch list above.  With a size m the loop
         # fits the logits of an m x m mask beside the latents, under the reference's mask objective; the image size is known in ``invert``
         self.mask_size = None
@@ -1599,7 +1697,7 @@ class WPlusInverter:
         return self._pins[i]
 
     def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None, noise_ids=None,
-               latent_anchor=None, pn_stats=None, pixel_target=None, mask_logits=None):
+               latent_anchor=None, pn_stats=None, pixel_target=None, mask_logits=None, align_init=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
         then share the GPU with the matrix kernels of the other instead of running back to back.
@@ -1613,8 +1711,22 @@ class WPlusInverter:
         ``pixel_size`` is an error) and replaces the view of ``target`` made here — the pooled target with the box, the resized one with a
         ``pixel_filter``.  ``target`` stays the full-size image LPIPS and SSIM, if on, compare with.  Not with a loss weight.
         ``mask_logits``: with ``mask_size`` = m, the float32 (B,1,m,m) start logits of the fitted mask on the device
-        (``mask_logits(a0)`` makes them from a start mask); required then, refused without it, and not beside a ``loss_weight``."""
+        (``mask_logits(a0)`` makes them from a start mask); required then, refused without it, and not beside a ``loss_weight``.
+        ``align_init``: with ``align``, the float32 (B,4) start of theta on the device, None = the identity; refused without
+        ``align``.  Afterwards ``last_alignment`` (B,4) is the fitted theta and ``last_aligned_target`` the target warped by it."""
         B = w0.shape[0]
+        self.last_alignment = self.last_aligned_target = None
+        if self.align is not None:
+            refuse_align(use_graph, self.lpips is not None and self.lpips_weight != 0.0, self.ssim_weight != 0.0,
+                         'full' if (loss_weight is None and self.mask_size is None) else 'blend' if self.mask_size is None else 'fit',
+                         self.pixel_filter, pixel_target, self.latent_space, self.feature_layer, self.engine.padded)
+            if target.dim() != 4 or min(target.shape[-2:]) < 4:
+                raise ValueError(f'align: the target must be (B,C,H,W) with H, W >= 4, got {tuple(target.shape)}')
+            check_align_init(align_init, B, target.device)
+            align_init = (torch.zeros(B, 4, device=target.device, dtype=torch.float32) if align_init is None
+                          else align_init.detach().contiguous())
+        elif align_init is not None:
+            raise ValueError('align_init without align: there is no alignment it could start')
         self.last_fitted_mask = self.last_mask_logits = self.last_loss_weight = None
         if self.mask_size is not None:
             refuse_mask_fit(use_graph, None if self.pixel_size == int(target.shape[-1]) else self.pixel_size, self.pixel_filter, pixel_target, self.latent_space, self.feature_layer, self.engine.padded)
@@ -1672,6 +1784,9 @@ class WPlusInverter:
             if self.mask_size is not None and B > 0:
                 self.last_mask_logits = mask_logits.clone()
                 self.last_fitted_mask, self.last_loss_weight = ops.maskfit_expand(self.last_mask_logits, int(target.shape[-1]))
+            if self.align is not None and B > 0:
+                self.last_alignment = align_init.clone()
+                self.last_aligned_target = ops.similarity_warp(target.contiguous(), self.last_alignment)
             return (w, empty, []) if return_trajectory else (w, empty)
         if return_trajectory:
             streams, use_graph = 1, False
@@ -1686,7 +1801,7 @@ class WPlusInverter:
         f0 = None if fshape is None else ops.zeros(B, *fshape, device=w0.device)
         try:
             return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0, pn,
-                                     pixel_target, mask_logits)
+                                     pixel_target, mask_logits, align_init if self.align is not None else None)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
@@ -1728,8 +1843,8 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None, ml0=None):
-        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px, ml0)] per stream; ``px``, the pixel target, and ``ml0``, the mask's start logits, are sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None, ml0=None, th0=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px, ml0, th0)] per stream; ``px``, the pixel target, ``ml0``, the mask's start logits, and ``th0``, the alignment's start, are sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
         ``pn``, the read-only statistics of the P_N+ prior, is shared by all of them.
         ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
         caller's own."""
@@ -1751,17 +1866,17 @@ class WPlusInverter:
                           None if ids is None else ids[sl].contiguous(),
                           anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor,
                           None if f0 is None else f0[sl].contiguous(), pn, None if px is None else px[sl].contiguous(),
-                          None if ml0 is None else ml0[sl].contiguous()))
+                          None if ml0 is None else ml0[sl].contiguous(), None if th0 is None else th0[sl].contiguous()))
         if on_side:
             for st in side:
                 st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
         return side, engines, parts
 
     @staticmethod
-    def _gather(side, w, tables, f=None, ml=None):
+    def _gather(side, w, tables, f=None, ml=None, th=None):
         """The per-stream latents (joined along the batch) and loss tables (``tables``: one list per term, None = term off; joined along the
         images) on the caller's stream; of a single run, its own tensors.  ``f``: the per-stream feature offsets, joined along the batch
-        like the latents and returned after the tables; ``ml``: the per-stream mask logits, the same way, returned last."""
+        like the latents and returned after the tables; ``ml``: the per-stream mask logits, the same way, returned after them; ``th``: the per-stream alignments, returned last."""
         cur = torch.cuda.current_stream()
         join = lambda ts, dim: ts[0] if len(ts) == 1 else torch.cat(ts, dim)
         for st in side:
@@ -1772,18 +1887,20 @@ class WPlusInverter:
             out.append(join(f, 0))
         if ml is not None:
             out.append(join(ml, 0))
-        for ts in [w] + tables + ([] if f is None else [f]) + ([] if ml is None else [ml]):     # tensors produced on side streams are consumed on the caller's stream
+        if th is not None:
+            out.append(join(th, 0))
+        for ts in [w] + tables + ([] if f is None else [f]) + ([] if ml is None else [ml]) + ([] if th is None else [th]):     # tensors produced on side streams are consumed on the caller's stream
             for t in ts:
                 if t is not None:
                     t.record_stream(cur)
         return out
 
     def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None, pn=None,
-                     px=None, ml0=None):
+                     px=None, ml0=None, th0=None):
         self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
         replay = 'graph' if use_graph else 'plan' if self.use_plan else None
         # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
-        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px, ml0)
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px, ml0, th0)
         runs = []
         try:
             for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):
@@ -1805,8 +1922,12 @@ class WPlusInverter:
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
                                                              [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs],
                                                              [r.ft_table for r in runs], [r.pn_table for r in runs], [r.ma_table for r in runs],
-                                                             [r.mb_table for r in runs]], None if f0 is None else [r.f for r in runs],
-                                 None if ml0 is None else [r.ml for r in runs])
+                                                             [r.mb_table for r in runs], [r.al_table for r in runs]],
+                                 None if f0 is None else [r.f for r in runs], None if ml0 is None else [r.ml for r in runs],
+                                 None if th0 is None else [r.th for r in runs])
+        if th0 is not None:         # the fitted theta and the target in its frame: one more warp, outside the step
+            self.last_alignment = tables.pop()
+            self.last_aligned_target = ops.similarity_warp(target.contiguous(), self.last_alignment)
         if ml0 is not None:         # a_T and beta_T of the fitted logits: one more expand, outside the step
             self.last_mask_logits = tables.pop()
             self.last_fitted_mask, self.last_loss_weight = ops.maskfit_expand(self.last_mask_logits, int(target.shape[-1]))
@@ -1818,9 +1939,9 @@ class WPlusInverter:
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None, ma=None, mb=None):
+    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None, ma=None, mb=None, al=None):
         self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl,
-                           'style': st, 'feature': ft, 'pn': pn, 'mask_area': ma, 'mask_binary': mb}
+                           'style': st, 'feature': ft, 'pn': pn, 'mask_area': ma, 'mask_binary': mb, 'align': al}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         total = total if lat is None else total + self.latent_reg * lat
@@ -1829,4 +1950,5 @@ class WPlusInverter:
         total = total if ft is None else total + self.feature_reg * ft
         total = total if pn is None else total + self.pn_reg * pn
         total = total if ma is None else total + self.mask_area_weight * ma
-        return total if mb is None else total + self.mask_binary_weight * mb
+        total = total if mb is None else total + self.mask_binary_weight * mb
+        return total if al is None else total + self.align_reg * al

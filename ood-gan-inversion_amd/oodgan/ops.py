@@ -1386,14 +1386,20 @@ def _pool_factor(f):
     return f
 
 
-def area_pool(x, f, grad_buffer=False):
+def area_pool(x, f, grad_buffer=False, out=None):
     """y = the mean of every f x f window of x (B,C,H,W) (oodgan_area_pool_fwd): F.avg_pool2d(x, f), summed in fp32 in row-major
     order and scaled by the exact 1/f^2.  f in {2, 4, 8, 16} with H % f == 0 and W % f == 0; the library refuses anything else.
     ``grad_buffer=True`` returns (y, gzero): gzero, of y's shape, zeroed by the same kernel — the buffer a loss term on y accumulates its
-    gradient into before ``area_pool_bwd_add`` (inside a recorded W+ step every fill has to come from this library)."""
+    gradient into before ``area_pool_bwd_add`` (inside a recorded W+ step every fill has to come from this library).  ``out``: a contiguous
+    float32 (B,C,H/f,W/f) tensor on x's device to write y into (a persistent buffer of the W+ loop); None: a new one."""
     a, f = _pool_image(x, 'x'), _pool_factor(f)
     B, C, H, W = a.shape
-    y = torch.empty(B, C, H // f, W // f, device=a.device, dtype=torch.float32)
+    if out is None:
+        y = torch.empty(B, C, H // f, W // f, device=a.device, dtype=torch.float32)
+    else:
+        y = out
+        assert tuple(y.shape) == (B, C, H // f, W // f) and y.dtype == torch.float32 and y.is_contiguous() and y.device == a.device, \
+            'area_pool: out must be a contiguous float32 (B,C,H/f,W/f) tensor on x\'s device'
     gz = torch.empty_like(y) if grad_buffer else None
     check(_lib.lib().oodgan_area_pool_fwd(_p(a), _p(y), _p(gz), B * C, H, W, f, _stream()), 'area_pool_fwd')
     return (y, gz) if grad_buffer else y
@@ -1924,3 +1930,79 @@ def maskfit_step(logit, g, m, v, a, e, t_dev, total_steps, rampup=0.0, rampdown=
                                          float(grad_div), float(area), float(area_weight), float(binary_weight), _p(area_table),
                                          _p(binary_table), nrows, _p(stat), _stream()), 'maskfit_step')
     return logit
+
+
+# ---- similarity alignment of the target beside the latents (csrc/loss_align.hip)
+def _theta(theta, B, device, name='theta'):
+    """theta as the alignment ops take it: a contiguous float32 (B, 4) tensor on ``device`` (no copy: the step updates in place)."""
+    if not isinstance(theta, torch.Tensor) or tuple(theta.shape) != (B, 4) or theta.dtype != torch.float32 or theta.device != device \
+            or not theta.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous float32 {(B, 4)} tensor on {device}: (log-scale, rotation, tx, ty) per image')
+    return theta
+
+
+def similarity_warp(img, theta, out=None):
+    """x_theta (B,C,H,W): ``img`` resampled by the per-image similarity theta (B, 4) = (log-scale lambda, rotation phi in radians, tx, ty in
+    ``affine_grid``'s normalised units) about the image centre (oodgan_similarity_warp) — F.grid_sample(img, F.affine_grid([[a, -s, tx],
+    [s, a, ty]]), mode='bicubic', padding_mode='border', align_corners=False) with a = e^lambda cos(phi), s = e^lambda sin(phi); the offsets
+    are formed in double.  theta = 0 returns img's bits.  ``out``: a contiguous float32 tensor of img's shape to write into (not img
+    itself); None: a new one.  H, W >= 4."""
+    a = _pool_image(img, 'img')
+    B, C, H, W = a.shape
+    th = _theta(theta, B, a.device)
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.shape == a.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == a.device and out.data_ptr() != a.data_ptr(), \
+        'similarity_warp: out must be another contiguous float32 tensor of img\'s shape on its device'
+    check(_lib.lib().oodgan_similarity_warp(_p(a), _p(th), _p(out), B, C, H, W, _stream()), 'similarity_warp')
+    return out
+
+
+def similarity_inverse(theta):
+    """theta^-1 = (-lambda, -phi, -e^-lambda R(-phi) t), computed on the host in float64 and returned in theta's dtype on its device:
+    ``similarity_warp(similarity_warp(x, theta), similarity_inverse(theta))`` is x again away from the border (up to two bicubic resamplings)."""
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.shape[1] != 4:
+        raise ValueError(f'theta must be a (B, 4) tensor, got {getattr(theta, "shape", theta)!r}')
+    th = theta.detach().to('cpu', torch.float64)
+    e, c, s = torch.exp(-th[:, 0]), torch.cos(th[:, 1]), torch.sin(th[:, 1])
+    tx = -e * (c * th[:, 2] + s * th[:, 3])
+    ty = -e * (c * th[:, 3] - s * th[:, 2])
+    return torch.stack([-th[:, 0], -th[:, 1], tx, ty], 1).to(theta.device, theta.dtype)
+
+
+def align_grad_parts(B, H, W, device):
+    """The (B, nparts, 6) float64 buffer ``align_grad_step`` reduces its sums through (oodgan_align_grad_nparts)."""
+    return torch.empty(B, max(1, _lib.lib().oodgan_align_grad_nparts(int(H), int(W))), 6, device=device, dtype=torch.float64)
+
+
+def align_grad_step(gimg, src, theta, g, m, v, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.001, betas=(0.9, 0.999), eps=1e-8,
+                    grad_div=1.0, align_reg=0.0, table=None, loss_out=None, part=None):
+    """The alignment's side of a W+ step (oodgan_align_grad_step).  ``gimg`` (B,C,H,W) is the step's image gradient dL/dG times ``grad_div``,
+    ``src`` the unwarped target; since the target enters the pixel term as G - x_theta, dL/dtheta = -sum gimg * dx_theta/dtheta / grad_div,
+    summed in double in two deterministic stages.  theta, g, m, v (B, 4) contiguous float32, updated in place: g receives the gradient plus
+    2 * ``align_reg`` * theta, what Adam consumes; Adam as ``feature_step`` — it reads ``t_dev``, uses t = t_dev[0] + 1 and leaves the counter
+    alone, so it runs BEFORE the latent-side call.  sum_k theta_k^2 (before the update) goes to row t_dev[0] (clamped) of ``table``
+    (nrows, B) or to ``loss_out`` (B,) — the sinks of the loss ops; with neither it is not written.  ``part``: the buffer of
+    ``align_grad_parts`` (made here when None).  ``lr`` 0 leaves theta unchanged.  Returns theta."""
+    a, x = _pool_image(gimg, 'gimg'), _pool_image(src, 'src')
+    if a.shape != x.shape or a.device != x.device:
+        raise ValueError(f'align_grad_step: gimg {tuple(a.shape)} and src {tuple(x.shape)} must have one shape on one device')
+    B, C, H, W = a.shape
+    for t, name in ((theta, 'theta'), (g, 'g'), (m, 'm'), (v, 'v')):
+        _theta(t, B, a.device, name)
+    assert t_dev.dtype == torch.int32 and t_dev.device == a.device
+    dst, nrows = None, 0
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and table.device == a.device
+        dst, nrows = table, table.shape[0]
+    elif loss_out is not None:
+        assert loss_out.shape == (B,) and loss_out.dtype == torch.float32 and loss_out.is_contiguous() and loss_out.device == a.device
+        dst, nrows = loss_out, 1
+    if part is None:
+        part = align_grad_parts(B, H, W, a.device)
+    assert (part.dtype == torch.float64 and part.is_contiguous() and part.device == a.device
+            and part.numel() >= 6 * B * _lib.lib().oodgan_align_grad_nparts(H, W)), 'align_grad_step: part must be the buffer of align_grad_parts'
+    check(_lib.lib().oodgan_align_grad_step(_p(a), _p(x), _p(theta), _p(g), _p(m), _p(v), B, C, H, W, float(lr), float(betas[0]),
+                                            float(betas[1]), float(eps), _p(t_dev), int(total_steps), float(rampup), float(rampdown),
+                                            float(grad_div), float(align_reg), _p(dst), nrows, _p(part), _stream()), 'align_grad_step')
+    return theta
