@@ -63,7 +63,7 @@ long oodgan_get_tunable(const char* name);
  * "t2big", "t2v2", "t2gen", "s2big", "s2v2", "s2gen", "upvb" (oodgan_upconv_vblur_fform), and the sub-counters of the fused epilogues:
  * "s1big_ys" (8-wave stride-1 launches that wrote `ys` / ToRGB partial sums), "s1big_g2" / "s2big_g2" / "stripx_g2" (input-gradient launches
  * that ran with x_hi_only, two matrix instructions per product), "s2big_xh" / "s1big_xh" (... on 32-byte hi-only input records, x_hi_only = 2), "s2big_fuse" (8-wave stride-2 launches with the fused activation
- * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]) and "align" (accepted calls of oodgan_similarity_warp / oodgan_align_grad_step); the backward producers: "blurt_strip" / "blurt_tile" (launches of the
+ * backward), "s2big_dotx_sform" (... that decoded `dotx` from a saved S-form), "composite_mse" (calls of oodgan_composite_mse_fwd_bwd[_row]), "ssim" (calls of oodgan_ssim_loss_fwd_bwd[_row]), "robust" (calls of oodgan_robust_loss_fwd_bwd[_row]), "area_pool" (accepted calls of oodgan_area_pool_fwd / oodgan_area_pool_bwd_add) "pooled_pixel" (accepted calls of oodgan_pooled_pixel_loss_fwd_bwd[_row]) "resampled_pixel" (accepted calls of oodgan_resampled_pixel_loss_fwd_bwd[_row]) "align" (accepted calls of oodgan_similarity_warp / oodgan_align_grad_step) and "color" (accepted calls of oodgan_color_pixel_loss_fwd_bwd[_row] / oodgan_color_step / oodgan_color_apply); the backward producers: "blurt_strip" / "blurt_tile" (launches of the
  * strip walk / the tile kernel of oodgan_act_bwd_blurT_sform_phases[_hi]), "actbwd_sform" (oodgan_act_bwd_sform) and "actbwd_sform_f" (oodgan_act_bwd_sform_f).  Host-side, one relaxed atomic increment per call; the reference has no
  * counterpart (cuDNN picks its algorithm silently) — the parity tests use them to assert which kernel they pinned.
  * Returns -1 for an unknown name. */
@@ -870,6 +870,40 @@ int oodgan_align_grad_nparts(int H, int W);
 int oodgan_align_grad_step(const float* gimg, const float* src, float* theta, float* g, float* m, float* v, int B, int C, int H, int W,
                            float lr, float beta1, float beta2, float eps, const int* t_dev, int total_steps, float rampup, float rampdown,
                            float grad_div, float align_reg, float* reg_table, int nrows, double* part, void* stream);
+/* Colour map of the generator image beside the latents of the W+ loop (csrc/loss_color.hip; entries added, ABI 117
+ * unchanged).  The reference names the nuisance (aug_inputcolor: ColorJitter on the encoder input, unusable there) and has no counterpart on
+ * the optimisation side.  theta (B, 12) float32 = (M row-major 3x3, b) per image, the identity (I, 0); images have C = 3.
+ *   c_i(p) = fma(M_i2, G_2, fma(M_i1, G_1, fma(M_i0, G_0, b_i)))            the mapped image, this one order everywhere, in double
+ *   d = float(c - x): the residual is rounded once, as the plain kernels' a - t; or beta d with a loss weight beta (B,1,H,W);  loss[b] = mean over 3 H W of rho(d), rho and psi the pixel terms' (kind 0:
+ *   the square, OODGAN_ROBUST_* otherwise, scale as oodgan_robust_loss_fwd_bwd);  g_i = gscale psi(d_i) (times beta once more), gscale =
+ *   grad_mul / (3 H W), twice that for the square: the plain kernels' wrt_gen gradient;  gimg_j = fma(M_2j, g_2, fma(M_1j, g_1, M_0j g_0)),
+ *   what the backward receives;  the 12 sums  S_ij = sum_p g_i G_j (slot 3 i + j),  S_i = sum_p g_i (slot 9 + i)  in double.
+ * At the identity with finite G: c == G and gimg == g, the plain kernels' gradient, bit for bit.
+ * fwd_bwd: one pass (read G, read x, write gimg; a thread owns four neighbouring pixels in all three planes; 16-byte accesses where
+ * H W % 4 == 0 and the pointers are 16-byte aligned, a scalar form otherwise), loss partials to `part` (B, oodgan_color_nparts) floats, finished by
+ * the mean kernel of every pixel term into loss[B] (or row min(row_dev[0], nrows - 1) of loss_table (nrows, B)); the 12 sums per block
+ * to `dpart` (B, oodgan_color_nparts, 12) doubles in a fixed order (a thread's pixels in index order, the wave's xor tree, the four waves
+ * in order).  No float atomics.  A null pointer (beta may be NULL), B outside [1, 65535], H or W outside [1, 32768], an unknown kind, a bad
+ * scale under the robust entries' rule, a NaN grad_mul: -1 and nothing is launched. */
+int oodgan_color_nparts(int H, int W);
+int oodgan_color_pixel_loss_fwd_bwd(const float* img, const float* target, const float* beta, const float* theta, float* gimg, float* part,
+                                    double* dpart, float* loss, int B, int H, int W, int kind, float scale, float grad_mul, void* stream);
+int oodgan_color_pixel_loss_fwd_bwd_row(const float* img, const float* target, const float* beta, const float* theta, float* gimg, float* part,
+                                        double* dpart, float* loss_table, const int* row_dev, int nrows, int B, int H, int W, int kind,
+                                        float scale, float grad_mul, void* stream);
+/* The colour map's side of a W+ step: one wave per image adds dpart (B, nparts, 12) in double in a fixed order, g_k = float(S_k / grad_div)
+ * + 2 color_reg (theta_k - id_k), the gradient of color_reg sum_k (theta_k - id_k)^2; bit k of free_mask clear: g_k = 0 and theta_k, m_k, v_k
+ * are not touched ('affine' 0xfff, 'gain' 0xf11: the diagonal and b).  g (B, 12) is written: what Adam consumed.  The sum over all 12
+ * numbers (before the update) goes to row min(t - 1, nrows - 1) of reg_table (nrows, B), NULL: not written.  Adam on theta with m, v
+ * (B, 12) as oodgan_feature_step: the same betas, eps and ramp factor r(t - 1) in double; launched BEFORE the latent-side call of the step,
+ * it reads t_dev[0], uses t = t_dev[0] + 1 and does NOT increment.  lr 0 leaves theta as it is.  A null pointer, B or nparts <= 0, a mask
+ * with bits above 12, lr < 0 (or NaN), color_reg < 0 (or NaN), grad_div <= 0, total_steps <= 0: -1 and nothing is launched. */
+int oodgan_color_step(float* theta, float* g, float* m, float* v, const double* dpart, int B, int nparts, int free_mask, float lr, float beta1,
+                      float beta2, float eps, const int* t_dev, int total_steps, float rampup, float rampdown, float grad_div, float color_reg,
+                      float* reg_table, int nrows, void* stream);
+/* out (B, 3, H, W) = M src + b per image, the fused multiply-adds of the term in its order, rounded to float once; out may be src.  theta = identity returns src's
+ * bits (finite src).  Null pointers and bad shapes as above: -1. */
+int oodgan_color_apply(const float* src, const float* theta, float* out, int B, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------ X1 LPIPS(alex) term ---- */
 /* The perceptual term of the inversion loss (north_star: "W+ Adam steps against LPIPS/L2"; reference call site

@@ -62,7 +62,9 @@ enum { OODGAN_DC_STRIPX = 0, OODGAN_DC_STRIP, OODGAN_DC_S1BIG, OODGAN_DC_S1V2, O
        // launches of the backward producers (bwd_producers.hip): blur^T strip walk / blur^T tile kernel / oodgan_act_bwd_sform / oodgan_act_bwd_sform_f
        OODGAN_DC_BLURT_STRIP, OODGAN_DC_BLURT_TILE, OODGAN_DC_ACTBWD_SFORM, OODGAN_DC_ACTBWD_SFORM_F,
        // accepted calls of the similarity alignment (loss_align.hip, oodgan_similarity_warp / oodgan_align_grad_step)
-       OODGAN_DC_ALIGN, OODGAN_DC_COUNT };
+       OODGAN_DC_ALIGN,
+       // accepted calls of the colour map (loss_color.hip, oodgan_color_pixel_loss_fwd_bwd[_row] / oodgan_color_step / oodgan_color_apply)
+       OODGAN_DC_COLOR, OODGAN_DC_COUNT };
 void count_dispatch(int id);
 
 // One process per GPU: per-kernel setup (dynamic-LDS attributes, the zero page and CU count of the F-form strip

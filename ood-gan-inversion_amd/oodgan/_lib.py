@@ -207,6 +207,12 @@ _SIGS = {
     'oodgan_align_grad_nparts': (c_int, [c_int, c_int]),
     'oodgan_align_grad_step': (c_int, [P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float,
                                        c_float, c_float, c_float, P, c_int, P, P]),
+    'oodgan_color_nparts': (c_int, [c_int, c_int]),
+    'oodgan_color_pixel_loss_fwd_bwd': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, P]),
+    'oodgan_color_pixel_loss_fwd_bwd_row': (c_int, [P, P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float, P]),
+    'oodgan_color_step': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, c_float, c_float, c_float, P, c_int, c_float, c_float, c_float,
+                                  c_float, P, c_int, P]),
+    'oodgan_color_apply': (c_int, [P, P, P, c_int, c_int, c_int, P]),
     'oodgan_latent_prior_fwd_bwd': (c_int, [P, P, P, P, c_int, c_long, c_int, c_float, P]),
     'oodgan_latent_prior_fwd_bwd_row': (c_int, [P, P, P, P, P, c_int, c_int, c_long, c_int, c_float, P]),
     'oodgan_pn_prior_fwd_bwd': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_float, P, P]),
@@ -265,7 +271,7 @@ def set_tunable(name, value):
 
 
 def dispatch_count(name):
-    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", the area-pool kernels, "area_pool", the pooled pixel-term kernel, "pooled_pixel", or the resampled pixel term, "resampled_pixel", or of the similarity alignment, "align", or launches of the backward producers, "blurt_strip" / "blurt_tile" / "actbwd_sform" / "actbwd_sform_f") since load /
+    """Calls of oodgan_conv3x3_f16s routed to kernel family ``name`` (or of the masked-loss kernel, "composite_mse", the SSIM loss kernel, "ssim", the robust pixel-loss kernel, "robust", the area-pool kernels, "area_pool", the pooled pixel-term kernel, "pooled_pixel", or the resampled pixel term, "resampled_pixel", or of the similarity alignment, "align", or of the colour map, "color", or launches of the backward producers, "blurt_strip" / "blurt_tile" / "actbwd_sform" / "actbwd_sform_f") since load /
     dispatch_reset() (include/oodgan.h)."""
     n = lib().oodgan_dispatch_count(name.encode())
     if n < 0:

@@ -15,7 +15,7 @@ import torch
 from torch import nn
 
 from . import ops, samm
-from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, mask_logits, refuse_mask_fit, check_align, check_align_init, refuse_align
+from .engine import WPlusInverter, check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_pixel_target, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, mask_logits, refuse_mask_fit, check_align, check_align_init, refuse_align, check_color, check_color_init, refuse_color
 from .modules import Generator
 from .synth import generator_channels
 
@@ -219,13 +219,18 @@ class ood_faceGAN_e4e(nn.Module):
         # feature offset (B, C, h, h) on the input of latent ``feature_layer``'s up-conv; a SAMM hook on that latent
         # receives the raw up-conv output as ever, which now includes the offset's effect
         fo = dict(feature_offset=kwargs.get('feature_offset', None), feature_layer=kwargs.get('feature_layer', None))
+        # fitted colour map theta (B,12) = (M, b): the generator image is mapped once, C(G) = M G + b, before the blend — the
+        # output alpha x + (1 - alpha) C(G) is in the photograph's colours, without a tint seam where the mask switches
+        color = kwargs.get('color', None)
         if self.modulation is None:
             out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs, **fo)
-            return out, lats
+            return (out if color is None else ops.color_apply(out.contiguous(), color)), lats
         out = self._hooked_generate(lats, enc_feats, noise, offs, **fo)
+        if self.blend_with_gen and self.skip_SA:
+            out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs, **fo)
+        if color is not None:
+            out = ops.color_apply(out.contiguous(), color)
         if self.blend_with_gen:
-            if self.skip_SA:
-                out, _ = self.generator(lats, input_is_tensor=True, input_is_latent=True, noise=noise, style_offsets=offs, **fo)
             for _ in range(self.blend_cnt):
                 out = self.blend(x, out, alpha_scale=None)
         return out, lats
@@ -271,7 +276,7 @@ class ood_faceGAN_e4e(nn.Module):
                delta_reg=0.0, style_reg=0.0, pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0,
                pn_samples=100000, pn_seed=0, pn_floor=0.0, pn_stats=None, pixel_filter=None, pixel_target=None, mask_size=64, mask_lr=0.1,
                mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, mask_init=0.88, fit_blend=False, align=None, align_lr=0.001,
-               align_reg=0.0, align_init=None, **kwargs):
+               align_reg=0.0, align_init=None, color=None, color_lr=0.002, color_reg=0.0, color_init=None, **kwargs):
         """Optimisation-based inversion: w0 = encoder latents (+avg+delta), ``steps``
         Adam steps on per-image MSE with fixed noise, then ONE full OOD forward with the refined
         latents (masks + blend).  Returns (out, lats, losses[steps,B]).  ``lpips_weight`` > 0 adds that multiple of LPIPS(alex) per image to the
@@ -405,7 +410,29 @@ class ood_faceGAN_e4e(nn.Module):
         without the option).  Goes with 'w+' / 'w', layer_lr, delta_reg, the schedule, pn_reg, edit, streams, the four pixel kinds and box
         ``pixel_size``.  ``use_graph``, LPIPS, SSIM, a ``loss_region`` other than 'full', a non-box ``pixel_filter``, ``pixel_target``,
         latent_space 's', feature_layer and a zero-padded (narrow) generator raise NotImplementedError (``engine.refuse_align``); a bad name,
-        rate, weight or start raises ValueError."""
+        rate, weight or start raises ValueError.
+        ``color='gain'`` or ``'affine'``: the loop fits, beside the latents, a colour map theta = (M row-major 3x3, b) per image
+        and takes the pixel term on C(G) = M G + b — a colour cast, another exposure, faded or sepia film is explained by twelve numbers
+        ('gain': six, per-channel gain and offset: white balance and exposure) instead of costing the latents identity and editability.
+        Adam with ``color_lr`` (0.002: at most 0.2 of gain, or 25 grey levels of offset, over 100 steps; a choice, nobody has measured it
+        as an optimum) under the loop's betas, eps and ramps; ``color_reg`` = mu >= 0 adds mu * sum_k (theta_k - id_k)^2 per image
+        (``last_loss_terms['color']``); ``color_init``: a float32 (B,12) start on the device, None = the identity.  The final OOD forward maps
+        the generator image once before the blend: the output is alpha x + (1 - alpha) C(G), in the photograph's colours (C(G) without
+        modulation); ``self.last_color`` is theta (None without the option) and ``model(x, lats=lats, color=self.last_color)`` reproduces the
+        output.  THE COLOUR-CORRECTED PICTURE is ``ops.color_apply(out, ops.color_inverse(theta))``: an affine map commutes with the blend, so
+        this is the blend of C^-1(x) with G.  With ``loss_region='blend'`` alpha_0 comes from the unmapped pass at w0, as without the option.
+        Goes with 'w+' / 'w', layer_lr, delta_reg, the schedule, pn_reg, edit, streams, the four pixel kinds and ``loss_region`` 'blend' or a
+        tensor.  ``use_graph``, LPIPS, SSIM, ``loss_region='fit'``, align, pixel_size, pixel_filter, pixel_target, latent_space 's',
+        feature_layer and a zero-padded (narrow) generator raise NotImplementedError (``engine.refuse_color``); a bad name, rate, weight or
+        start raises ValueError."""
+        color, color_lr, color_reg = check_color(color, color_lr, color_reg)
+        if color is not None:       # every check of the option before any device work; the refusals in one place (engine.refuse_color)
+            refuse_color(use_graph, bool(lpips_weight), ssim_weight != 0.0, loss_region if isinstance(loss_region, str) else 'a loss-weight tensor',
+                         align, None if pixel_size == int(x.shape[-1]) else pixel_size, pixel_filter, pixel_target, latent_space, feature_layer)
+            refuse_color(padded=self.generator.engine().padded)
+            check_color_init(color_init, x.shape[0], x.device)
+        elif color_init is not None:
+            raise ValueError('color_init without color: there is no colour map it could start')
         align, align_lr, align_reg = check_align(align, align_lr, align_reg)
         feats_of = None
         if align is not None:       # every check of the option before any device work; the refusals in one place (engine.refuse_align)
@@ -505,11 +532,13 @@ class ood_faceGAN_e4e(nn.Module):
                             pixel_loss=pixel_loss, pixel_scale=pixel_scale, lpips_size=lpips_size, latent_space=latent_space, layer_lr=layer_lr,
                             delta_reg=delta_reg, style_reg=style_reg, pixel_size=pixel_size, feature_layer=feature_layer, feature_lr=feature_lr,
                             feature_reg=feature_reg, pn_reg=pn_reg, pixel_filter=pixel_filter, mask_size=mask_size if fit else None,
-                            mask_lr=mask_lr, mask_area=mask_area, mask_area_weight=mask_area_weight, mask_binary_weight=mask_binary_weight, align=align, align_lr=align_lr, align_reg=align_reg)
+                            mask_lr=mask_lr, mask_area=mask_area, mask_area_weight=mask_area_weight, mask_binary_weight=mask_binary_weight, align=align, align_lr=align_lr, align_reg=align_reg,
+                            color=color, color_lr=color_lr, color_reg=color_reg)
         w, losses = inv.invert(x, lats0, noise, steps=steps, streams=streams, use_graph=use_graph, loss_weight=beta, noise_ids=noise_ids,
-                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target, mask_logits=ml0, align_init=align_init)
+                               latent_anchor=anchor, pn_stats=pn_stats, pixel_target=pixel_target, mask_logits=ml0, align_init=align_init, color_init=color_init)
         self.last_fitted_mask = inv.last_fitted_mask
         self.last_alignment, self.last_aligned_input = inv.last_alignment, inv.last_aligned_target
+        self.last_color = inv.last_color
         if align is not None:       # the output is made in the aligned frame: the encoder features, the forward and the blend see x_a
             x = self.last_aligned_input
             if feats_of is not None:
@@ -520,7 +549,9 @@ class ood_faceGAN_e4e(nn.Module):
             self.last_loss_weight = inv.last_loss_weight
         self.last_loss_terms, self.last_invert_stats, self.last_invert_plan = inv.last_terms, inv.last_stats, inv.last_plan
         kw = {k: v for k, v in kwargs.items() if k not in ('noise_passes', 'truncation', 'enc_lats', 'enc_feats', 'lats', 'noise', 'style_offsets',
-                                                           'feature_offset')}
+                                                           'feature_offset', 'color')}
+        if self.last_color is not None:
+            kw.update(color=self.last_color)
         self.last_feature_offset, self.last_feature_layer = inv.last_feature_offset, (feature_layer if inv.last_feature_offset is not None else None)
         if self.last_feature_offset is not None:
             kw.update(feature_offset=self.last_feature_offset, feature_layer=feature_layer)

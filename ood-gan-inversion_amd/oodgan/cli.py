@@ -31,6 +31,14 @@ Where the W+ loss looks, in the same block:
                                  align_lr (0.001: about half a pixel per step at 1024²; not a measured optimum; >= 0), align_reg (0:
                                  the weight of sum theta^2; >= 0).  Not with lpips_weight, ssim_weight, loss_region other than full,
                                  mask_dir, a non-box pixel_filter, pixel_target, latent_space: s or feature_layer.  A bad value is an error.
+    color: gain | affine         the loop fits, beside the latents, a colour map (M, b) per image and takes the pixel term on M G + b
+                                 (DESIGN.md §26): a colour cast, another exposure or faded film is explained by twelve numbers (gain: six,
+                                 per-channel gain and offset) instead of costing the latents.  The saved inversion blends the input with the
+                                 MAPPED generator image: it is in the input's colours.  The fitted map itself is not saved.
+                                 color_lr (0.002: at most 0.2 of gain or 25 grey levels of offset over 100 steps; a choice, not a measured
+                                 optimum; >= 0), color_reg (0: the weight of sum (theta - identity)^2; >= 0).  Goes with loss_region: blend
+                                 and mask_dir.  Not with lpips_weight, ssim_weight, loss_region: fit, align, pixel_size, pixel_filter /
+                                 pixel_target, latent_space: s or feature_layer.  A bad value is an error.
     mask_dir: <dir>              a caller mask per input file: <dir>/<base name>.png (grayscale; the first channel / 255 is beta,
                                  0 = ignore the pixel), resized nearest to the generator size.  A file without a mask is an error.
                                  Excludes ``loss_region: blend``.
@@ -119,7 +127,7 @@ import yaml
 
 from . import imgio
 from .arch import ood_faceGAN_e4e, ood_faceGAN_FeatureStyle, ood_faceGAN_restyle
-from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, refuse_mask_fit, check_align, refuse_align
+from .engine import check_latent_controls, check_style_space, check_lpips_size, check_noise_seed, check_pixel_filter, check_pixel_loss, check_pixel_size, check_nonneg, check_feature_offset, check_feature_layer, check_pn_options, check_mask_fit, check_mask_init, refuse_mask_fit, check_align, refuse_align, check_color, refuse_color
 from .io import load_direction, load_network_g
 
 model_dict = {                                   # run_ood_faceGAN_inversion.py:23-27
@@ -301,6 +309,25 @@ def align_options(inv):
     return dict(align=kind, align_lr=rate, align_reg=reg)
 
 
+COLOR_KEYS = ('color', 'color_lr', 'color_reg')
+
+
+def color_options(inv):
+    """``inversion.color`` / ``color_lr`` / ``color_reg`` for ``model.invert``, checked one by one (ValueError names the option;
+    NotImplementedError for what the colour map does not go with) — before the GPU is touched.  {} without ``color``; either of the other
+    two without it is an error."""
+    if inv.get('color') is None:
+        stray = [k for k in COLOR_KEYS[1:] if k in inv]
+        if stray:
+            raise ValueError(f'inversion.{stray[0]} needs inversion.color')
+        return {}
+    kind, rate, reg = check_color(inv['color'], inv.get('color_lr', 0.002), inv.get('color_reg', 0.0), 'inversion.')
+    refuse_color(False, bool(inv.get('lpips_weight', 0.0)), bool(inv.get('ssim_weight', 0.0)), inv.get('loss_region', 'full'), inv.get('align'),
+                 inv.get('pixel_size'), check_pixel_filter(inv.get('pixel_filter'), 'inversion.pixel_filter'), inv.get('pixel_target'),
+                 inv.get('latent_space', 'w+'), inv.get('feature_layer'))
+    return dict(color=kind, color_lr=rate, color_reg=reg)
+
+
 def pn_options(inv):
     """``inversion.pn_reg`` / ``pn_samples`` / ``pn_seed`` / ``pn_floor`` for ``model.invert``, checked one by one and against
     ``inversion.latent_space`` (ValueError names the option) — before the GPU is touched."""
@@ -468,6 +495,7 @@ def run(opts, wplus_steps=None, log=None):
     sched.update(pn_options(inv))
     sched.update(fit_opts)
     sched.update(align_options(inv))
+    sched.update(color_options(inv))
     edit_at = edit_option(inv)
     steps = int(wplus_steps if wplus_steps is not None else inv.get('wplus_steps', 0))
     directions_dir = opts.get('directions_dir', './directions')

@@ -853,9 +853,20 @@ class _WRun:
     repeated window draws the same noise and takes the same learning rates."""
 
     def __init__(self, inv, eng, target, w0, noises, steps, stream, keep_traj, replay, beta=None, ids=None, anchor=None, f0=None, pn=None,
-                 px=None, ml0=None, th0=None):
+                 px=None, ml0=None, th0=None, c0=None):
         self.inv, self.eng, self.stream, self.steps = inv, eng, stream, steps
         self.target, self.noises = target, noises
+        # colour map (DESIGN.md §26): a leaf beside the latents — theta (B,12) = (M, b) from ``c0``, its moments, the gradient Adam consumed,
+        # the float and double partial sums of the fused term and the buffer it writes M^T g into.  All persistent and born here, never
+        # inside a recorded step (see ``replay`` below); ``color_reg`` brings a loss table
+        self.ct = self.ctm = self.ctv = self.ctg = self.cparts = self.cgimg = self.co_table = None
+        if c0 is not None:
+            self.ct = c0.detach().clone().contiguous()
+            self.ctm, self.ctv, self.ctg = (torch.zeros_like(self.ct) for _ in range(3))
+            self.cparts = ops.color_parts(self.ct.shape[0], target.shape[-2], target.shape[-1], target.device)
+            self.cgimg = torch.empty_like(target, memory_format=torch.contiguous_format)
+            if inv.color_reg != 0.0:
+                self.co_table = torch.zeros(steps, self.ct.shape[0], device=self.ct.device, dtype=torch.float32)
         # similarity alignment (DESIGN.md §25): a leaf beside the latents — theta (B,4) from ``th0``, its moments and the gradient Adam consumed.
         # ``src`` keeps the photograph; ``target`` becomes the buffer x_theta the warp rewrites in front of every forward, so that
         # ``_loss_grad`` reads it where it read the photograph (with ``pixel_size`` the pooled target below is re-made from it every step as
@@ -951,7 +962,7 @@ class _WRun:
         self.traj = [None] * steps if keep_traj else None
         self.mode0 = (eng.fused_bwd, eng.carry_range)            # what the caller asked for (tests run the exact loop on purpose)
         self.guard = (eng.fused_bwd or eng.carry_range) and inv.check_every > 0 and replay != 'graph'
-        self.clean = (0, self.w.clone(), None, None, self._fsnap(), self._msnap(), self._asnap()) if self.guard else None     # m = v = 0 at t = 0
+        self.clean = (0, self.w.clone(), None, None, self._fsnap(), self._msnap(), self._asnap(), self._csnap()) if self.guard else None     # m = v = 0 at t = 0
         self.pending, self.exact_until = None, 0
         self.steps_run = 0                                       # forward/backward pairs enqueued, repeated windows included
         self.rollbacks = 0
@@ -1011,6 +1022,15 @@ class _WRun:
             ops.align_grad_step(gimg, self.src, self.th, self.thg, self.thm, self.thv, self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown,
                                 inv.align_lr, inv.betas, inv.eps, grad_div=self.gmul, align_reg=inv.align_reg, table=self.al_table,
                                 part=self.apart)
+        elif self.ct is not None:
+            # the colour map as a second leaf: forward and backward are the plain step's, ``_loss_grad`` takes the pixel term on M G + b in
+            # one fused pass that hands M^T g to the backward and leaves the sums of dL/dtheta; its side of the step is one launch, placed
+            # BEFORE the latent-side call, which increments the counter both read
+            img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
+            gimg = self._loss_grad(img)
+            g = eng.backward(gimg, self.gmul, carry_scale=True)
+            ops.color_step(self.ct, self.ctg, self.ctm, self.ctv, self.cparts[1], self.dev_t, self.steps, inv.lr_rampup, inv.lr_rampdown,
+                           inv.color_lr, inv.betas, inv.eps, grad_div=self.gmul, kind=inv.color, color_reg=inv.color_reg, table=self.co_table)
         elif self.f is None:
             img = eng.forward(w_in, self.noises, save=True, range_mode='carry')
             gimg = self._loss_grad(img)
@@ -1046,6 +1066,10 @@ class _WRun:
          the pixel term always writes dL/dc (and c only if LPIPS or SSIM reads it), and ``maskfit_chain`` takes the place of
         ``scale_by_plane``: the same pass also leaves dL/dbeta = sum_c dL/dc_c (G_c - x_c) in ``me``, whatever terms added to dL/dc."""
         inv, gmul, row = self.inv, self.gmul, self.dev_t
+        if self.ct is not None:                 # the fused term of the colour map in the pixel term's place (no other term goes with it)
+            _, gimg, _ = ops.color_pixel_loss_grad(img, self.target, self.ct, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, table=self.lbuf,
+                                                   row_dev=row, parts=self.cparts, out=self.cgimg)
+            return gimg
         fit = self.ml is not None
         on_c = self.beta is not None and (self.lp is not None or self.ss_table is not None)
         _, gimg, c = ops.pixel_loss_grad(img, self.target, inv.pixel_loss, inv.pixel_scale, self.beta, gmul, wrt='composite' if (on_c or fit) else 'gen',
@@ -1112,9 +1136,13 @@ class _WRun:
         """(th, thm, thv) as they stand, for a snapshot; None without an alignment."""
         return None if self.th is None else (self.th.clone(), self.thm.clone(), self.thv.clone())
 
+    def _csnap(self):
+        """(ct, ctm, ctv) as they stand, for a snapshot; None without a colour map."""
+        return None if self.ct is None else (self.ct.clone(), self.ctm.clone(), self.ctv.clone())
+
     def _post_check(self):
         eng = self.eng
-        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap(), self._asnap())
+        snap = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap(), self._asnap(), self._csnap())
         ev = torch.cuda.Event()
         ev.record()
         side, done = _flag_stream(self.w.device), torch.cuda.Event()
@@ -1137,7 +1165,7 @@ class _WRun:
             self.clean = snap
             return False
         eng = self.eng
-        t0, w, m, v, fs, ms, als = self.clean
+        t0, w, m, v, fs, ms, als, cs = self.clean
         self.w.copy_(w)
         if m is None:
             self.m.zero_()
@@ -1153,6 +1181,9 @@ class _WRun:
                 dst.copy_(src)
         if als is not None:                                      # ... and the alignment and its moments
             for dst, src in zip((self.th, self.thm, self.thv), als):
+                dst.copy_(src)
+        if cs is not None:                                       # ... and the colour map and its moments
+            for dst, src in zip((self.ct, self.ctm, self.ctv), cs):
                 dst.copy_(src)
         self.t = t0
         self.dev_t.fill_(t0)
@@ -1171,7 +1202,7 @@ class _WRun:
         eng.reset_fwd_state()
         self.exact_until = 0
         self.eager_left = self.warmup
-        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap(), self._asnap())
+        self.clean = (self.t, self.w.clone(), self.m.clone(), self.v.clone(), self._fsnap(), self._msnap(), self._asnap(), self._csnap())
 
     def _advance(self):
         if self.t < self.steps:
@@ -1548,6 +1579,56 @@ def refuse_align(use_graph=False, lpips=False, ssim=False, loss_region='full', p
                                       f"pixel_size) of the 'w+' / 'w' loop under launch plans")
 
 
+COLOR_KINDS = ('gain', 'affine')      # the colour maps the W+ loop fits beside the latents
+
+
+def check_color(color=None, color_lr=0.002, color_reg=0.0, prefix=''):
+    """The options of the fitted colour map as (color, color_lr, color_reg): ValueError, naming the option, unless ``color`` is
+    None or one of COLOR_KINDS, ``color_lr`` a finite number >= 0 (0 keeps theta at its start) and ``color_reg`` a finite number >= 0.
+    Without ``color`` the other two are not looked at.  The default rate 0.002 is a choice — at most 0.2 of gain, or 25 grey levels of
+    offset, over 100 steps — and not a measured optimum."""
+    if color is None:
+        return None, 0.002, 0.0
+    if not isinstance(color, str) or color not in COLOR_KINDS:
+        raise ValueError(f'{prefix}color must be None or one of {list(COLOR_KINDS)}, got {color!r}')
+    rate = _finite_real(color_lr, prefix + 'color_lr', 'a finite number >= 0')
+    reg = _finite_real(color_reg, prefix + 'color_reg', 'a finite number >= 0')
+    if rate < 0.0 or reg < 0.0:
+        raise ValueError(f'{prefix}color_lr / {prefix}color_reg must be finite numbers >= 0, got {color_lr!r}, {color_reg!r}')
+    return color, rate, reg
+
+
+def check_color_init(value, B=None, device=None, name='color_init'):
+    """``color_init``, the start of theta: None (the identity) or a float32 (B, 12) tensor of finite values — (M row-major 3x3, b) per image —
+    on ``device`` (batch and device are checked once they are known).  ValueError otherwise."""
+    if value is None:
+        return None
+    if not isinstance(value, torch.Tensor) or value.dtype != torch.float32 or value.dim() != 2 or value.shape[1] != 12:
+        raise ValueError(f'{name} must be None or a float32 (B, 12) tensor (M row-major 3x3, then b), got '
+                         f'{getattr(value, "dtype", type(value).__name__)} {tuple(getattr(value, "shape", ()))}')
+    if B is not None and (value.shape[0] != B or value.device != torch.device(device)):
+        raise ValueError(f'{name} must be a float32 {(B, 12)} tensor on {device}, got {tuple(value.shape)} on {value.device}')
+    if not bool(torch.isfinite(value).all()):
+        raise ValueError(f'{name} must hold finite values')
+    return value
+
+
+def refuse_color(use_graph=False, lpips=False, ssim=False, loss_region='full', align=None, pixel_size=None, pixel_filter=None, pixel_target=None,
+                 latent_space='w+', feature_layer=None, padded=False):
+    """What the fitted colour map does not go with, refused in this one place before anything is launched: its fused kernel
+    is the full-resolution pixel term, and LPIPS and SSIM would have to see the mapped image.  ``loss_region``: 'full', 'blend' and a loss
+    weight go with it, 'fit' does not."""
+    for on, what in ((use_graph, 'use_graph'), (lpips, 'the LPIPS term'), (ssim, 'the SSIM term'),
+                     (loss_region == 'fit', "loss_region 'fit' (a fitted mask)"), (align is not None, f'align {align!r}'),
+                     (pixel_size is not None, 'pixel_size'), (pixel_filter is not None, f'pixel_filter {pixel_filter!r}'),
+                     (pixel_target is not None, 'pixel_target'), (latent_space == 's', "latent_space 's'"),
+                     (feature_layer is not None, 'feature_layer'),
+                     (padded, 'a generator whose channel counts are zero-padded to multiples of 16')):
+        if on:
+            raise NotImplementedError(f"color with {what}: the colour map is built for the full-resolution pixel term (every kind, with or "
+                                      f"without a loss weight) of the 'w+' / 'w' loop under launch plans")
+
+
 def check_noise_seed(value, name='noise_seed'):
     """The seed of the latent noise as an int; ValueError unless it is an integer in [0, 2^63)."""
     if isinstance(value, bool) or not isinstance(value, int) or not 0 <= value < 2 ** 63:
@@ -1619,6 +1700,18 @@ class WPlusInverter:
     NotImplementedError) with ``use_graph``, LPIPS, SSIM, a loss weight or a fitted mask, pixel_filter / pixel_target, latent_space 's',
     feature_layer and a zero-padded generator.
 
+    Fitted colour map.  ``color='gain'`` or ``'affine'``: beside the latents the loop fits theta = (M row-major 3x3, b) per image,
+    from ``invert(color_init=)`` (None: the identity), and takes the pixel term on C(G) = M G + b — a colour cast, an exposure or faded film
+    is explained by twelve numbers ('gain': six, the diagonal of M and b — white balance and exposure) instead of by the latents.  The
+    generator image is mapped, not the photograph: with the map on the target (M, b) -> (0, const) would shrink any residual.  One fused
+    pass (``ops.color_pixel_loss_grad``) gives the term, M^T g for the backward and the sums of dL/dtheta; ``ops.color_step`` is Adam with
+    ``color_lr`` (0.002: at most 0.2 of gain or 25 grey levels of offset over 100 steps; a choice, not a measured optimum) and the loop's
+    betas, eps and ramps: one launch more per step.  ``color_reg`` = mu >= 0 adds mu * sum_k (theta_k - id_k)^2 per image
+    (``last_terms['color']``).  Result: ``last_color`` (B,12); ``ops.color_apply(G, last_color)`` is the mapped image.  Goes with 'w+' and 'w',
+    layer_lr, delta_reg, the schedule, pn_reg, the four pixel kinds, a loss weight and streams; refused (``refuse_color``, NotImplementedError)
+    with ``use_graph``, LPIPS, SSIM, a fitted mask, align, pixel_size, pixel_filter / pixel_target, latent_space 's', feature_layer and a
+    zero-padded generator.
+
     ``check_every`` / ``check_lag``: the range guard of ``_WRun`` (0 = flags read only by the caller).  ``last_stats`` after a call:
     {'steps_run': forward/backward pairs enqueued per (sub-)batch, 'rollbacks': windows repeated with exact scales}; ``last_plan``:
     {'steps': steps replayed per (sub-)batch, from the plan or the graph, 'launches': launches of the recorded plan (0: none, or a graph)}."""
@@ -1627,8 +1720,14 @@ class WPlusInverter:
                  ssim_weight=0.0, lr_rampup=0.0, lr_rampdown=0.0, latent_noise=0.0, noise_ramp=0.75, noise_seed=0, latent_reg=0.0,
                  pixel_loss='mse', pixel_scale=0.1, lpips_size=None, latent_space='w+', layer_lr=None, delta_reg=0.0, style_reg=0.0,
                  pixel_size=None, feature_layer=None, feature_lr=None, feature_reg=0.0, pn_reg=0.0, pixel_filter=None, mask_size=None,
-                 mask_lr=0.1, mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, align=None, align_lr=0.001, align_reg=0.0):
+                 mask_lr=0.1, mask_area=0.30, mask_area_weight=5.0, mask_binary_weight=0.2, align=None, align_lr=0.001, align_reg=0.0,
+                 color=None, color_lr=0.002, color_reg=0.0):
         self.engine, self.lr, self.betas, self.eps = engine, lr, betas, eps
+        # fitted colour map, off by default (``color`` None): the step is then the launch list above.  'gain' / 'affine': beside
+        # the latents the loop fits theta = (M, b) per image and takes the pixel term on M G + b.  The default rate 0.002 allows at most 0.2
+        # of gain, or 25 grey levels of offset, over 100 steps: a choice, nobody has measured it as an optimum
+        self.color, self.color_lr, self.color_reg = check_color(color, color_lr, color_reg)
+        self.last_color = None
         # fitted alignment, off by default (``align`` None): the step is then the launch list above.  'similarity': beside the
         # latents the loop fits theta = (log-scale, rotation, tx, ty) per image and compares G(w) with the target warped by it.  The default
         # rate 0.001 moves a translation by about half a pixel per step at 1024² (tx is in units of half the image side); nobody has
@@ -1697,7 +1796,7 @@ class WPlusInverter:
         return self._pins[i]
 
     def invert(self, target, w0, noises, steps=100, return_trajectory=False, streams=1, use_graph=False, loss_weight=None, noise_ids=None,
-               latent_anchor=None, pn_stats=None, pixel_target=None, mask_logits=None, align_init=None):
+               latent_anchor=None, pn_stats=None, pixel_target=None, mask_logits=None, align_init=None, color_init=None):
         """``streams`` > 1 splits the batch into that many independent sub-batches, each advanced on its own HIP
         stream (images are independent): the HBM-bound layout/activation kernels of one sub-batch
         then share the GPU with the matrix kernels of the other instead of running back to back.
@@ -1713,8 +1812,22 @@ class WPlusInverter:
         ``mask_logits``: with ``mask_size`` = m, the float32 (B,1,m,m) start logits of the fitted mask on the device
         (``mask_logits(a0)`` makes them from a start mask); required then, refused without it, and not beside a ``loss_weight``.
         ``align_init``: with ``align``, the float32 (B,4) start of theta on the device, None = the identity; refused without
-        ``align``.  Afterwards ``last_alignment`` (B,4) is the fitted theta and ``last_aligned_target`` the target warped by it."""
+        ``align``.  Afterwards ``last_alignment`` (B,4) is the fitted theta and ``last_aligned_target`` the target warped by it.
+        ``color_init``: with ``color``, the float32 (B,12) start of theta = (M, b) on the device, None = the identity; refused
+        without ``color``.  Afterwards ``last_color`` (B,12) is the fitted theta."""
         B = w0.shape[0]
+        self.last_color = None
+        if self.color is not None:
+            refuse_color(use_graph, self.lpips is not None and self.lpips_weight != 0.0, self.ssim_weight != 0.0,
+                         'fit' if self.mask_size is not None else 'full', self.align,
+                         None if self.pixel_size == int(target.shape[-1]) else self.pixel_size, self.pixel_filter, pixel_target,
+                         self.latent_space, self.feature_layer, self.engine.padded)
+            if target.dim() != 4 or target.shape[1] != 3:
+                raise ValueError(f'color: the target must be (B,3,H,W), got {tuple(target.shape)}')
+            check_color_init(color_init, B, target.device)
+            color_init = ops.color_identity(B, target.device) if color_init is None else color_init.detach().contiguous()
+        elif color_init is not None:
+            raise ValueError('color_init without color: there is no colour map it could start')
         self.last_alignment = self.last_aligned_target = None
         if self.align is not None:
             refuse_align(use_graph, self.lpips is not None and self.lpips_weight != 0.0, self.ssim_weight != 0.0,
@@ -1784,6 +1897,8 @@ class WPlusInverter:
             if self.mask_size is not None and B > 0:
                 self.last_mask_logits = mask_logits.clone()
                 self.last_fitted_mask, self.last_loss_weight = ops.maskfit_expand(self.last_mask_logits, int(target.shape[-1]))
+            if self.color is not None:
+                self.last_color = color_init.clone()
             if self.align is not None and B > 0:
                 self.last_alignment = align_init.clone()
                 self.last_aligned_target = ops.similarity_warp(target.contiguous(), self.last_alignment)
@@ -1801,7 +1916,8 @@ class WPlusInverter:
         f0 = None if fshape is None else ops.zeros(B, *fshape, device=w0.device)
         try:
             return self._invert_runs(target, w0, noises, steps, streams, return_trajectory, use_graph, loss_weight, ids, anchor, f0, pn,
-                                     pixel_target, mask_logits, align_init if self.align is not None else None)
+                                     pixel_target, mask_logits, align_init if self.align is not None else None,
+                                     color_init if self.color is not None else None)
         finally:
             if override:
                 _lib.set_tunable('s1_big_min_items', _S1_BIG_DEFAULT)
@@ -1843,8 +1959,8 @@ class WPlusInverter:
             anchor = anchor.detach().contiguous()
         return ids, anchor
 
-    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None, ml0=None, th0=None):
-        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px, ml0, th0)] per stream; ``px``, the pixel target, ``ml0``, the mask's start logits, and ``th0``, the alignment's start, are sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
+    def _split(self, target, w0, noises, beta, streams, on_side, ids=None, anchor=None, f0=None, pn=None, px=None, ml0=None, th0=None, c0=None):
+        """(streams, engines, [(target, w0, noises, beta, ids, anchor, f0, pn, px, ml0, th0, c0)] per stream; ``px``, the pixel target, ``ml0``, the mask's start logits, ``th0``, the alignment's start, and ``c0``, the colour map's, are sliced like the target): sub-batch i is images [(i*B)//streams, ((i+1)*B)//streams);
         ``pn``, the read-only statistics of the P_N+ prior, is shared by all of them.
         ``on_side``: the sub-batches run on side streams that wait for the caller's; otherwise (one sub-batch) the stream is None, the
         caller's own."""
@@ -1866,17 +1982,18 @@ class WPlusInverter:
                           None if ids is None else ids[sl].contiguous(),
                           anchor[sl].contiguous() if (anchor is not None and anchor.dim() == w0.dim()) else anchor,
                           None if f0 is None else f0[sl].contiguous(), pn, None if px is None else px[sl].contiguous(),
-                          None if ml0 is None else ml0[sl].contiguous(), None if th0 is None else th0[sl].contiguous()))
+                          None if ml0 is None else ml0[sl].contiguous(), None if th0 is None else th0[sl].contiguous(),
+                          None if c0 is None else c0[sl].contiguous()))
         if on_side:
             for st in side:
                 st.wait_stream(cur)             # AFTER the slices above were enqueued on the caller's stream
         return side, engines, parts
 
     @staticmethod
-    def _gather(side, w, tables, f=None, ml=None, th=None):
+    def _gather(side, w, tables, f=None, ml=None, th=None, ct=None):
         """The per-stream latents (joined along the batch) and loss tables (``tables``: one list per term, None = term off; joined along the
         images) on the caller's stream; of a single run, its own tensors.  ``f``: the per-stream feature offsets, joined along the batch
-        like the latents and returned after the tables; ``ml``: the per-stream mask logits, the same way, returned after them; ``th``: the per-stream alignments, returned last."""
+        like the latents and returned after the tables; ``ml``: the per-stream mask logits, the same way, returned after them; ``th``: the per-stream alignments, after them; ``ct``: the per-stream colour maps, returned last."""
         cur = torch.cuda.current_stream()
         join = lambda ts, dim: ts[0] if len(ts) == 1 else torch.cat(ts, dim)
         for st in side:
@@ -1889,18 +2006,20 @@ class WPlusInverter:
             out.append(join(ml, 0))
         if th is not None:
             out.append(join(th, 0))
-        for ts in [w] + tables + ([] if f is None else [f]) + ([] if ml is None else [ml]) + ([] if th is None else [th]):     # tensors produced on side streams are consumed on the caller's stream
+        if ct is not None:
+            out.append(join(ct, 0))
+        for ts in [w] + tables + ([] if f is None else [f]) + ([] if ml is None else [ml]) + ([] if th is None else [th]) + ([] if ct is None else [ct]):     # tensors produced on side streams are consumed on the caller's stream
             for t in ts:
                 if t is not None:
                     t.record_stream(cur)
         return out
 
     def _invert_runs(self, target, w0, noises, steps, streams, return_trajectory, use_graph, beta=None, ids=None, anchor=None, f0=None, pn=None,
-                     px=None, ml0=None, th0=None):
+                     px=None, ml0=None, th0=None, c0=None):
         self._graphs = []                       # the graphs of the call before (and their private pools) lived until here
         replay = 'graph' if use_graph else 'plan' if self.use_plan else None
         # a hipGraph cannot be captured on the default stream: a graph run takes a side stream also when it is the only one
-        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px, ml0, th0)
+        side, engines, parts = self._split(target, w0, noises, beta, streams, use_graph or streams > 1, ids, anchor, f0, pn, px, ml0, th0, c0)
         runs = []
         try:
             for st, eng, (x, w, nz, *rest) in zip(side, engines, parts):
@@ -1922,9 +2041,11 @@ class WPlusInverter:
         w, *tables = self._gather(side, [r.w for r in runs], [[r.lbuf for r in runs], [r.lp_table for r in runs], [r.ss_table for r in runs],
                                                              [r.lat_table for r in runs], [r.dl_table for r in runs], [r.st_table for r in runs],
                                                              [r.ft_table for r in runs], [r.pn_table for r in runs], [r.ma_table for r in runs],
-                                                             [r.mb_table for r in runs], [r.al_table for r in runs]],
+                                                             [r.mb_table for r in runs], [r.al_table for r in runs], [r.co_table for r in runs]],
                                  None if f0 is None else [r.f for r in runs], None if ml0 is None else [r.ml for r in runs],
-                                 None if th0 is None else [r.th for r in runs])
+                                 None if th0 is None else [r.th for r in runs], None if c0 is None else [r.ct for r in runs])
+        if c0 is not None:          # the fitted colour map
+            self.last_color = tables.pop()
         if th0 is not None:         # the fitted theta and the target in its frame: one more warp, outside the step
             self.last_alignment = tables.pop()
             self.last_aligned_target = ops.similarity_warp(target.contiguous(), self.last_alignment)
@@ -1939,9 +2060,9 @@ class WPlusInverter:
         losses = self._total(*tables)
         return (w, losses, runs[0].traj) if return_trajectory else (w, losses)
 
-    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None, ma=None, mb=None, al=None):
+    def _total(self, mse, lp, ss=None, lat=None, dl=None, st=None, ft=None, pn=None, ma=None, mb=None, al=None, co=None):
         self.last_terms = {'pixel': mse, 'mse': mse if self.pixel_loss == 'mse' else None, 'lpips': lp, 'ssim': ss, 'latent': lat, 'delta': dl,
-                           'style': st, 'feature': ft, 'pn': pn, 'mask_area': ma, 'mask_binary': mb, 'align': al}
+                           'style': st, 'feature': ft, 'pn': pn, 'mask_area': ma, 'mask_binary': mb, 'align': al, 'color': co}
         total = mse if lp is None else mse + self.lpips_weight * lp
         total = total if ss is None else total + self.ssim_weight * ss
         total = total if lat is None else total + self.latent_reg * lat
@@ -1951,4 +2072,5 @@ class WPlusInverter:
         total = total if pn is None else total + self.pn_reg * pn
         total = total if ma is None else total + self.mask_area_weight * ma
         total = total if mb is None else total + self.mask_binary_weight * mb
-        return total if al is None else total + self.align_reg * al
+        total = total if al is None else total + self.align_reg * al
+        return total if co is None else total + self.color_reg * co

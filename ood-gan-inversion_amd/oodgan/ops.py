@@ -2006,3 +2006,133 @@ def align_grad_step(gimg, src, theta, g, m, v, t_dev, total_steps, rampup=0.0, r
                                             float(betas[1]), float(eps), _p(t_dev), int(total_steps), float(rampup), float(rampdown),
                                             float(grad_div), float(align_reg), _p(dst), nrows, _p(part), _stream()), 'align_grad_step')
     return theta
+
+
+# ---- colour map of the generator image beside the latents (csrc/loss_color.hip)
+COLOR_KINDS = {'affine': 0xfff, 'gain': 0xf11}      # the free numbers of theta as a 12-bit mask: everything / the diagonal of M and b
+
+
+def _color_theta(theta, B, device, name='theta'):
+    """theta as the colour ops take it: a contiguous float32 (B, 12) tensor on ``device`` (no copy: the step updates in place)."""
+    if not isinstance(theta, torch.Tensor) or tuple(theta.shape) != (B, 12) or theta.dtype != torch.float32 or theta.device != device \
+            or not theta.is_contiguous():
+        raise ValueError(f'{name} must be a contiguous float32 {(B, 12)} tensor on {device}: (M row-major 3x3, b) per image')
+    return theta
+
+
+def _color_image(img, name):
+    a = _pool_image(img, name)
+    if a.shape[1] != 3:
+        raise ValueError(f'{name} must have 3 channels: the colour map is a 3x3 matrix and an offset, got {tuple(a.shape)}')
+    return a
+
+
+def color_identity(B, device):
+    """The identity map (I, 0) for B images: a float32 (B, 12) tensor on ``device``."""
+    return torch.tensor([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0], dtype=torch.float32).repeat(B, 1).to(device)
+
+
+def color_apply(img, theta, out=None):
+    """C_theta(img) (B,3,H,W) = M img + b per image (oodgan_color_apply), theta (B, 12) float32 = (M row-major 3x3, b); the fused
+    multiply-adds of the colour term in its order, so the identity returns img's bits.  ``out``: a contiguous float32 tensor of img's shape
+    to write into (img itself is allowed); None: a new one.  The colour-corrected picture of an inversion made with ``color`` is
+    ``color_apply(out, color_inverse(theta))``: an affine map commutes with the blend."""
+    a = _color_image(img, 'img')
+    B, _, H, W = a.shape
+    th = _color_theta(theta, B, a.device)
+    if out is None:
+        out = torch.empty_like(a)
+    assert out.shape == a.shape and out.dtype == torch.float32 and out.is_contiguous() and out.device == a.device, \
+        'color_apply: out must be a contiguous float32 tensor of img\'s shape on its device'
+    check(_lib.lib().oodgan_color_apply(_p(a), _p(th), _p(out), B, H, W, _stream()), 'color_apply')
+    return out
+
+
+def color_inverse(theta):
+    """theta^-1 = (M^-1, -M^-1 b), computed on the host in float64 and returned in theta's dtype on its device:
+    ``color_apply(color_apply(x, theta), color_inverse(theta))`` is x again.  ValueError for a singular or non-finite M."""
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 2 or theta.shape[1] != 12:
+        raise ValueError(f'theta must be a (B, 12) tensor, got {getattr(theta, "shape", theta)!r}')
+    th = theta.detach().to('cpu', torch.float64)
+    if not bool(torch.isfinite(th).all()):
+        raise ValueError('color_inverse: theta must hold finite values')
+    M, b = th[:, :9].reshape(-1, 3, 3), th[:, 9:]
+    if M.shape[0]:
+        det = torch.linalg.det(M)
+        scale = M.abs().amax((1, 2)).clamp_min(1e-300) ** 3
+        if bool((det.abs() <= 1e-12 * scale).any()):
+            raise ValueError(f'color_inverse: M is singular (determinants {det.tolist()})')
+    Mi = torch.linalg.inv(M)
+    return torch.cat([Mi.reshape(-1, 9), -(Mi @ b.unsqueeze(-1)).squeeze(-1)], 1).to(theta.device, theta.dtype)
+
+
+def color_parts(B, H, W, device):
+    """(part, dpart): the (B, nparts) float32 and (B, nparts, 12) float64 buffers the colour term reduces through (oodgan_color_nparts)."""
+    n = max(1, _lib.lib().oodgan_color_nparts(int(H), int(W)))
+    return torch.empty(B, n, device=device, dtype=torch.float32), torch.empty(B, n, 12, device=device, dtype=torch.float64)
+
+
+def color_pixel_loss_grad(img, target, theta, kind='mse', scale=None, beta=None, grad_mul=1.0, loss_out=None, table=None, row_dev=None,
+                          parts=None, out=None):
+    """The pixel term on the colour-mapped image (oodgan_color_pixel_loss_fwd_bwd[_row]): per-image mean of rho(d),
+    d = C_theta(img) - target, or beta * that with a loss weight ``beta`` (B,1,H,W); ``kind`` and ``scale`` as ``pixel_loss_grad``.  One pass
+    writes gimg = M^T g, g the plain kernels' ``wrt='gen'`` gradient of the mapped image (grad_mul included), and leaves the 12 sums
+    sum g_i G_j, sum g_i per block in ``parts[1]`` for ``color_step``.  At the identity gimg is ``pixel_loss_grad``'s gradient bit for bit.
+    The sinks ``loss_out`` / ``table`` + ``row_dev`` are those of the loss ops.  ``parts``: the buffers of ``color_parts`` (made here when
+    None); ``out``: a contiguous float32 tensor of img's shape for the gradient.  Returns (loss[B] or None with ``table``, gimg, parts)."""
+    a, t = _color_image(img, 'img'), _color_image(target, 'target')
+    if a.shape != t.shape or a.device != t.device:
+        raise ValueError(f'color_pixel_loss_grad: img {tuple(a.shape)} and target {tuple(t.shape)} must have one shape on one device')
+    if kind != 'mse' and kind not in ROBUST_KINDS:
+        raise ValueError(f"kind must be 'mse' or one of {sorted(ROBUST_KINDS)}, got {kind!r}")
+    B, _, H, W = a.shape
+    th = _color_theta(theta, B, a.device)
+    w = None if beta is None else _plane(beta, a)
+    L = _lib.lib()
+    if parts is None:
+        parts = color_parts(B, H, W, a.device)
+    part, dpart = parts
+    n = L.oodgan_color_nparts(H, W)
+    assert (part.dtype == torch.float32 and dpart.dtype == torch.float64 and part.is_contiguous() and dpart.is_contiguous()
+            and part.device == a.device and dpart.device == a.device and part.numel() >= B * n and dpart.numel() >= 12 * B * n), \
+        'color_pixel_loss_grad: parts must be the buffers of color_parts'
+    g = torch.empty_like(a) if out is None else out
+    assert g.shape == a.shape and g.dtype == torch.float32 and g.is_contiguous() and g.device == a.device
+    dst, row, nrows, by_row, loss = _loss_sink(B, a.device, loss_out, table, row_dev)
+    sink = (_p(dst), _p(row), nrows) if by_row else (_p(dst),)
+    name = 'color_pixel_loss_fwd_bwd' + ('_row' if by_row else '')
+    check(getattr(L, 'oodgan_' + name)(_p(a), _p(t), _p(w), _p(th), _p(g), _p(part), _p(dpart), *sink, B, H, W,
+                                       0 if kind == 'mse' else ROBUST_KINDS[kind], 0.0 if kind == 'mse' else float(scale), float(grad_mul),
+                                       _stream()), name)
+    return loss, g, parts
+
+
+def color_step(theta, g, m, v, dpart, t_dev, total_steps, rampup=0.0, rampdown=0.0, lr=0.002, betas=(0.9, 0.999), eps=1e-8, grad_div=1.0,
+               kind='affine', color_reg=0.0, table=None, loss_out=None):
+    """The colour map's side of a W+ step (oodgan_color_step).  ``dpart`` (B, nparts, 12) float64: the sums ``color_pixel_loss_grad`` left;
+    they are added in double in a fixed order, divided by ``grad_div`` and rounded once.  theta, g, m, v (B, 12) contiguous float32, updated
+    in place: g receives the gradient plus 2 * ``color_reg`` * (theta - identity), what Adam consumes, and 0 where ``kind`` ('affine': all 12
+    numbers, 'gain': the diagonal of M and b; or the 12-bit mask itself) leaves a number fixed — theta, m and v of such a number are not
+    touched.  Adam as ``feature_step``: it reads ``t_dev``, uses t = t_dev[0] + 1 and leaves the counter alone, so it runs BEFORE the
+    latent-side call.  sum_k (theta_k - id_k)^2 (before the update) goes to row t_dev[0] (clamped) of ``table`` (nrows, B) or to ``loss_out``
+    (B,); with neither it is not written.  ``lr`` 0 leaves theta unchanged.  Returns theta."""
+    if not isinstance(theta, torch.Tensor) or not theta.is_cuda:
+        raise RuntimeError('theta must be a ROCm (cuda) tensor: the HIP path has no CPU fallback')
+    B = theta.shape[0]
+    for t, name in ((theta, 'theta'), (g, 'g'), (m, 'm'), (v, 'v')):
+        _color_theta(t, B, theta.device, name)
+    mask = COLOR_KINDS[kind] if isinstance(kind, str) else int(kind)
+    assert t_dev.dtype == torch.int32 and t_dev.device == theta.device
+    assert dpart.dtype == torch.float64 and dpart.dim() == 3 and dpart.shape[0] == B and dpart.shape[2] == 12 and dpart.is_contiguous() \
+        and dpart.device == theta.device, 'color_step: dpart must be the (B, nparts, 12) float64 buffer of color_parts'
+    dst, nrows = None, 0
+    if table is not None:
+        assert table.dim() == 2 and table.shape[1] == B and table.dtype == torch.float32 and table.is_contiguous() and table.device == theta.device
+        dst, nrows = table, table.shape[0]
+    elif loss_out is not None:
+        assert loss_out.shape == (B,) and loss_out.dtype == torch.float32 and loss_out.is_contiguous() and loss_out.device == theta.device
+        dst, nrows = loss_out, 1
+    check(_lib.lib().oodgan_color_step(_p(theta), _p(g), _p(m), _p(v), _p(dpart), B, dpart.shape[1], mask, float(lr), float(betas[0]),
+                                       float(betas[1]), float(eps), _p(t_dev), int(total_steps), float(rampup), float(rampdown),
+                                       float(grad_div), float(color_reg), _p(dst), nrows, _stream()), 'color_step')
+    return theta
